@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: output tokens/s (whole node) + p50 per-token latency, Llama-3-70B, PP=N.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +14,19 @@ in flight so all N stages stay busy while tokens return to the driver.  Work per
 fixed as N grows, so the scaling mode is "weak".  A "step" = every in-flight sequence decodes one token.  Timed region:
 barrier + device sync -> exactly K decode steps -> barrier + device sync; the max over ranks is
 reported.  Prefill and W warmup steps (incl. hipGraph capture) run before the timed region.
+
+A plain run does only what the headline figure needs.  The decode steps need every sequence's
+prompt in the KV cache, not 512 separate prefills (25 s of a 35 s run on one MI355X): a single
+in-process stage prefills as many prompts as fit one step (``--max-batched-tokens``), the other
+sequences reuse those prompts round-robin, and their KV blocks are copied on the device into blocks
+of their own (``_replicate_prefill``).  Batch, context length, block count and the kernels of the timed
+steps are those of a full prefill.  ``--full`` prefills every (distinct) prompt through the engine
+as a server would and reports that time as ``prefill_s``; multi-stage pipelines always do.
+
+``--dump-outputs DIR`` writes what the timed steps returned to their caller, the sampled token ids,
+after the timed window: ``DIR/tokens.npy`` (last step, one per sequence) and
+``DIR/tokens_timed.npy`` ([K, sequences]), float32.  Weights, prompts and sampling are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 ``--dp D`` (default 1) instead runs D independent pipeline replicas of N/D stages each (DP x PP:
 e.g. dp8 = eight whole-model Llama-3-70B replicas, one per GPU; dp2 x pp4).  Every replica's
@@ -73,6 +86,13 @@ def parse():
                          "stage at PP=8, so 8 ranks x 9 micro-batches x 512 rows fit one GPU); the "
                          "result names the reduced model and is not a headline number")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the timed steps' sampled tokens to DIR/tokens.npy (last step) and "
+                         "DIR/tokens_timed.npy ([steps, sequences]) as float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: prefill every "
+                         "prompt through the engine (prefill_s) instead of replicating the KV "
+                         "of one step's worth of prompts")
     return ap.parse_args()
 
 
@@ -130,6 +150,89 @@ def _rank_record(node, rank: int, window_s: float) -> dict:
     return rec
 
 
+def _tuning_dir() -> None:
+    """The engine keeps its hipBLASLt tuning results under ``build/tuning`` of the source tree
+    (``DLI_TUNING_DIR`` moves them).  A benchmark run from a tree this user may not write to keeps
+    them in the user's cache directory instead, or in a temporary one."""
+    if os.environ.get("DLI_TUNING_DIR"):
+        return
+    import tempfile
+    home = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.expanduser("~/.cache"),
+                        "distributed_llm_inference", "tuning")
+    for d in (os.path.join(REPO, "build", "tuning"), home):
+        try:
+            os.makedirs(d, exist_ok=True)
+            with tempfile.TemporaryFile(dir=d):
+                pass
+        except OSError:
+            continue
+        if not d.startswith(REPO + os.sep):
+            os.environ["DLI_TUNING_DIR"] = d
+        return
+    os.environ["DLI_TUNING_DIR"] = tempfile.mkdtemp(prefix="dli_tuning_")
+
+
+def _adopt(sched, seq, mb: int) -> None:
+    """Book ``seq`` into micro-batch ``mb`` of the scheduler as a decoding sequence: the state
+    admission and a finished prefill step leave (``Scheduler._admit`` / ``plan``).  Its prompt's KV
+    is in the cache of every stage and ``seq.output`` holds its first sampled token."""
+    from distributed_llm_inference.runtime.sequence import SeqStatus
+    if len(seq.output) != 1 or seq.status is not SeqStatus.WAITING:
+        raise ValueError("needs a waiting sequence with exactly its first token sampled")
+    if len(seq.prompt) + seq.params.max_tokens > sched.max_seq_len:
+        raise ValueError("prompt + max_tokens exceeds max_seq_len")
+    if len(sched.mbs[mb]) >= sched.max_seqs:
+        raise ValueError(f"micro-batch {mb} is full")
+    need = sched.blocks_for(seq.total_len)
+    if sched.reserved_blocks + need > sched.total_blocks:
+        raise MemoryError("the sequence does not fit in the KV cache")
+    sched.reserved_blocks += need
+    sched._reserve[seq.seq_id] = need
+    sched._n_admitted += 1
+    sched._order[seq.seq_id] = sched._n_admitted
+    seq.status = SeqStatus.RUNNING
+    seq.micro_batch = mb
+    seq.num_computed = len(seq.prompt)
+    sched.mbs[mb].append(seq)
+    sched._dirty[mb] = True
+    sched.max_running = max(sched.max_running, sched.num_running())
+
+
+def _replicate_prefill(drv, src, clones) -> None:
+    """Give every sequence of ``clones`` the prompt KV of ``src[i % len(src)]`` (prefilled, first
+    token sampled, not yet decoding) in KV blocks of its own on every stage, and hand it to the
+    scheduler as a running sequence.  ``clones[i].prompt`` is that source's prompt."""
+    import torch
+    P = len(src[0].prompt)
+    ids = [c.seq_id for c in clones]
+    for ex in drv.executors:
+        m, pool = ex.pool.manager, ex.pool
+        ex.reserve(ids, [P] * len(ids))
+        sb, db = [], []
+        for i, c in enumerate(clones):
+            s_t, d_t = m.block_table(src[i % len(src)].seq_id), m.block_table(c.seq_id)
+            assert len(s_t) == len(d_t), (len(s_t), len(d_t))
+            sb += s_t
+            db += d_t
+        si = torch.tensor(sb, dtype=torch.long, device=pool.device)
+        di = torch.tensor(db, dtype=torch.long, device=pool.device)
+        for t in (pool.k, pool.v):
+            raw = t.view(torch.int16 if t.element_size() == 2 else torch.uint8)   # bit copies
+            for layer in range(pool.num_layers):
+                raw[layer].index_copy_(0, di, raw[layer].index_select(0, si))
+    for i, c in enumerate(clones):
+        c.append_token(src[i % len(src)].output[0], drv.sched.eos)
+        _adopt(drv.sched, c, 0)
+
+
+def _dump_outputs(path: str, seqs, steps: int) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    timed = np.asarray([s.output[-steps:] for s in seqs], dtype=np.float32).T   # [steps, G]
+    np.save(os.path.join(path, "tokens_timed.npy"), np.ascontiguousarray(timed))
+    np.save(os.path.join(path, "tokens.npy"), np.ascontiguousarray(timed[-1]))
+
+
 def main():
     a = parse()
     import torch
@@ -151,6 +254,7 @@ def main():
     dp, pp = a.dp, a.gpus // a.dp
     os.environ.setdefault("DLI_PROGRESS", "1")   # init phases on stderr (runtime/engine.py)
     _heartbeat()
+    _tuning_dir()
     if rank == 0:
         _build.build_all()
     if world > 1:
@@ -214,19 +318,31 @@ def main():
     rng = random.Random(1234 + 7919 * getattr(drv, "replica", 0))
     # generous max_tokens (above): none may finish inside the timed window (constant batch)
     params = SamplingParams(max_tokens=max_tokens, ignore_eos=True)
-    seqs = [Sequence([rng.randrange(spec.vocab_size) for _ in range(a.prompt_len)], params)
-            for _ in range(G)]
-    for s in seqs:
+    prompts = [[rng.randrange(spec.vocab_size) for _ in range(a.prompt_len)] for _ in range(G)]
+    # a plain run of one in-process stage prefills one step's worth of prompts and replicates
+    # their KV (module docstring); everything else prefills every prompt
+    n_src = max(1, min(G, a.max_batched_tokens // a.prompt_len))
+    replicate = (not a.full and hasattr(drv, "executors") and drv.sched.M == 1 and n_src < G)
+    if replicate:
+        prompts = [prompts[i % n_src] for i in range(G)]
+    seqs = [Sequence(p, params) for p in prompts]
+    first = seqs[:n_src] if replicate else seqs
+    for s in first:
         drv.sched.add(s)
     # prefill: run until every sequence produced its first token
     t_pf = time.perf_counter()
-    _progress(f"prefill of {G} prompts x {a.prompt_len} tokens")
+    _progress(f"prefill of {len(first)} prompts x {a.prompt_len} tokens")
     n_rounds = 0
-    while any(len(s.output) == 0 for s in seqs):
+    while any(len(s.output) == 0 for s in first):
         drv.round()
         n_rounds += 1
         if n_rounds % 20 == 0:
-            _progress(f"prefill: {sum(len(s.output) > 0 for s in seqs)}/{G} prompts done")
+            _progress(f"prefill: {sum(len(s.output) > 0 for s in first)}/{len(first)} prompts done")
+    if replicate:
+        if any(len(s.output) != 1 for s in first):
+            raise RuntimeError("prefilled prompts started decoding before their KV was replicated")
+        _progress(f"replicating their KV for the other {G - n_src} sequences")
+        _replicate_prefill(drv, first, seqs[n_src:])
     prefill_s = time.perf_counter() - t_pf
     _progress(f"prefill done in {prefill_s:.1f}s; warmup")
     for _ in range(a.warmup):
@@ -298,6 +414,7 @@ def main():
         "prompt_len": a.prompt_len,
         "tokens_timed": toks,
         "prefill_s": round(prefill_s, 3),
+        "prompts_prefilled": len(first),
         # host time of the driver rank per micro-batch step NOT spent waiting for results
         "driver_host_ms_per_mb_step": round(driver_busy / (a.steps * M) * 1e3, 3),
         # ... and by phase (runtime/hostclock.py; waits on the device / token channel apart)
@@ -327,6 +444,8 @@ def main():
         # the headline metric names its model; a run of another model says what it measured
         res["metric"] = (f"output tokens/sec (whole node) + p50 token latency, "
                          f"{res['config']['model']} PP={pp}")
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, seqs, a.steps)
     line = json.dumps(res)
     print(line, flush=True)
     if a.json_out:

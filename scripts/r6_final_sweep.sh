@@ -6,7 +6,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 600 python -u bench.py "$@" --json-out $out/$name.json > $out/$name.log 2>&1 || { tail -20 $out/$name.log; exit 1; }
+  timeout -k 10 600 python -u bench.py "$@" --full --json-out $out/$name.json > $out/$name.log 2>&1 || { tail -20 $out/$name.log; exit 1; }
   python -c "import json; d=json.load(open('$out/$name.json')); print('$name', 'prefill_s', d['prefill_s'], 'tok/s', d['value'], 'ms/step', d['ms_per_step'])"
 }
 run headline

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gemm_gpu.py -x -q --timeout 200
 tail -1 $out/gemm_tests.log
 run() {  # name, policy, args...
   local name=$1 pol=$2; shift 2
-  DLI_KERNELS=$pol timeout -k 10 600 python -u bench.py "$@" --json-out $out/$name.json > $out/$name.log 2>&1 || { tail -20 $out/$name.log; exit 1; }
+  DLI_KERNELS=$pol timeout -k 10 600 python -u bench.py "$@" --full --json-out $out/$name.json > $out/$name.log 2>&1 || { tail -20 $out/$name.log; exit 1; }
   python -c "import json; d=json.load(open('$out/$name.json')); print('$name', 'prefill_s', d['prefill_s'], 'tok/s', d['value'])"
 }
 for pol in tile_gemm_max_m=0 tile_gemm_max_m=2048; do
