@@ -33,9 +33,13 @@ def _common(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--dp", type=int, default=1,
                     help="pipeline replicas (data parallel); each gets gpus/dp stages")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--fp8", action="store_true", help="fp8-e4m3 weights")
-    ap.add_argument("--int8", action="store_true",
+    wq = ap.add_mutually_exclusive_group()
+    wq.add_argument("--fp8", action="store_true", help="fp8-e4m3 weights")
+    wq.add_argument("--int8", action="store_true",
                     help="LLM.int8 weights (int8 MFMA + bf16 outlier columns), the reference's mode")
+    wq.add_argument("--fp4", action="store_true",
+                    help="MXFP4 weights (4-bit e2m1 + e8m0 scale per 32: 17/32 byte per "
+                         "parameter; the interactive-decode and KV-capacity mode)")
     ap.add_argument("--int8-threshold", type=float, default=6.0,
                     help="LLM.int8 outlier threshold (bitsandbytes / reference default 6.0 / 5.0)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
@@ -68,7 +72,8 @@ def engine_config(a):
     return EngineConfig(
         kernels=KernelPolicy().with_overrides(getattr(a, "kernels", "")),
         model=a.model, checkpoint=a.checkpoint, random_init=a.checkpoint is None, seed=a.seed,
-        quantize="fp8" if a.fp8 else ("int8" if a.int8 else False),
+        quantize=("fp8" if a.fp8 else "int8" if a.int8
+                  else "mxfp4" if getattr(a, "fp4", False) else False),
         int8_threshold=a.int8_threshold, pp=a.gpus // max(1, a.dp), dp=a.dp,
         cache=CacheConfig(block_size=a.block_size, gpu_memory_utilization=a.gpu_mem,
                           window_length=a.window, num_sink_tokens=a.sinks, dtype=a.kv_dtype),
@@ -93,7 +98,10 @@ def cmd_plan(a) -> int:
     layout = ReplicaLayout.for_world(a.gpus, a.dp)
     rotate = layout.pp > 1 and os.environ.get("DLI_HEAD_ROTATION", "1") == "1"
     ranges = plan_stages(spec, layout.pp, head_rotation=rotate)
-    per_layer = spec.layer_param_count() * (1 if (a.fp8 or a.int8) else 2)
+    # bytes per layer parameter: MXFP4 = a nibble + one scale byte per 32 (the norm weights, a
+    # few thousand bf16 values per layer, are not told apart)
+    per_param = 17 / 32 if a.fp4 else (1 if (a.fp8 or a.int8) else 2)
+    per_layer = int(spec.layer_param_count() * per_param)
     emb = spec.vocab_size * spec.hidden_size * 2
     replicas = []
     for r in range(layout.dp):
@@ -109,6 +117,7 @@ def cmd_plan(a) -> int:
                             kv_capacity_tokens=int(max(0, free) // kv_tok)))
         replicas.append(dict(replica=r, driver_rank=r * layout.pp, stages=out))
     res = {"model": spec.name, "num_layers": spec.num_layers, "dp": layout.dp, "pp": layout.pp,
+           "weight_bytes_per_param": per_param,
            "lm_head": "rotating over the pipeline ranks (decode)" if rotate else "last stage",
            "layout": f"dp{layout.dp}xpp{layout.pp}" if layout.dp > 1 else f"pp{layout.pp}",
            "stages": replicas[0]["stages"]}

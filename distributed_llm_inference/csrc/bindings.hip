@@ -877,21 +877,78 @@ void skinny_gemm_fp8(Tensor out, Tensor x, optional<Tensor> xscale, Tensor w, Te
            "skinny_gemm_fp8");
 }
 
+// MXFP4 weights: e2m1 nibbles [N, K / 2] (uint8) + e8m0 block exponents [N, K / 32] (uint8), bf16
+// rows, M <= 2
+static void check_mxfp4(const Tensor& w, const Tensor& bscale, int64_t K, const char* what) {
+  CHECK_IN(w); CHECK_IN(bscale);
+  TORCH_CHECK(w.scalar_type() == at::kByte && bscale.scalar_type() == at::kByte, what,
+              ": MXFP4 weights and block scales are uint8");
+  TORCH_CHECK(w.dim() == 2 && bscale.dim() == 2 && K >= 32 && K % 32 == 0 && w.size(1) == K / 2 &&
+                  bscale.size(0) == w.size(0) && bscale.size(1) == K / 32,
+              what, ": w [N, K / 2], block_scale [N, K / 32], K % 32 == 0");
+}
+
+void skinny_gemm_fp4(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Tensor> bias,
+                     bool swiglu, optional<Tensor> norm_w, optional<Tensor> res_in,
+                     optional<Tensor> res_out, double eps) {
+  const GemvNormArgs na = gemv_norm_args(x, norm_w, res_in, res_out, eps, "skinny_gemm_fp4");
+  CHECK_IN(out); CHECK_IN(x);
+  CHECK_BF16(out); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "skinny_gemm_fp4: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1);
+  check_mxfp4(w, bscale, K, "skinny_gemm_fp4");
+  const int64_t N = w.size(0);
+  TORCH_CHECK(M >= 1 && M <= 2, "skinny_gemm_fp4: M in [1, 2]");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == gemv_out_cols(N, swiglu, "skinny_gemm_fp4"),
+              "skinny_gemm_fp4: shape mismatch");
+  const dli::bf16* b = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N, "skinny_gemm_fp4: bias must have N entries");
+    b = bp(*bias);
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_skinny_gemm_fp4(bp(out), bp(x), w.data_ptr<uint8_t>(),
+                                       bscale.data_ptr<uint8_t>(), b, (int)M, (int)N, (int)K,
+                                       cur_stream(), swiglu, na.on ? &na.nm : nullptr),
+           "skinny_gemm_fp4");
+}
+
+// out (bf16, contiguous, N * K elements) = the dequantised MXFP4 weight [N, K]
+void dequant_mxfp4(Tensor out, Tensor w, Tensor bscale) {
+  CHECK_IN(out); CHECK_BF16(out);
+  TORCH_CHECK(w.dim() == 2, "dequant_mxfp4: w [N, K / 2]");
+  const int64_t N = w.size(0), K = w.size(1) * 2;
+  check_mxfp4(w, bscale, K, "dequant_mxfp4");
+  TORCH_CHECK(out.numel() == N * K && out.device() == w.device(),
+              "dequant_mxfp4: out must hold N * K bf16 on the weight's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  check_rc(dli::launch_dequant_mxfp4(bp(out), w.data_ptr<uint8_t>(), bscale.data_ptr<uint8_t>(),
+                                     (size_t)(N * (K / 32)), cur_stream()),
+           "dequant_mxfp4");
+}
+
 // 1-2 decode rows: the fused QKV GEMV whose epilogue does rope_cache's work (q rotated into q_out,
 // k rotated and v written into the paged caches), optionally with the fused input RMSNorm.
-// w: bf16 [N, K], fp8 e4m3 / int8 [N, K] with fp32 per-row wscale; N = (nh + 2 nkv) D.
+// w: bf16 [N, K], fp8 e4m3 / int8 [N, K] with fp32 per-row wscale, or (block_scale given) MXFP4
+// nibbles [N, K / 2] with e8m0 block exponents [N, K / 32]; N = (nh + 2 nkv) D.
 void skinny_gemm_qkv_rope(Tensor q_out, Tensor x, Tensor w, optional<Tensor> wscale,
                           optional<Tensor> bias, optional<Tensor> positions,
                           optional<Tensor> slot_mapping, optional<Tensor> cos_sin, Tensor k_cache,
                           Tensor v_cache, int64_t nh, int64_t nkv, double k_scale, double v_scale,
                           optional<Tensor> norm_w, optional<Tensor> res_in,
-                          optional<Tensor> res_out, double eps) {
+                          optional<Tensor> res_out, double eps, optional<Tensor> block_scale) {
   CHECK_IN(q_out); CHECK_IN(x); CHECK_IN(w);
   CHECK_BF16(q_out); CHECK_BF16(x);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && q_out.dim() == 3, "skinny_gemm_qkv_rope: shapes");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0), D = q_out.size(2);
-  TORCH_CHECK(M >= 1 && M <= 2 && w.size(1) == K && q_out.size(0) == M && q_out.size(1) == nh &&
-                  N == (nh + 2 * nkv) * D,
+  const bool fp4 = block_scale.has_value();
+  if (fp4) {
+    TORCH_CHECK(!wscale.has_value(), "skinny_gemm_qkv_rope: block_scale (MXFP4) excludes wscale");
+    check_mxfp4(w, *block_scale, K, "skinny_gemm_qkv_rope");
+  }
+  TORCH_CHECK(M >= 1 && M <= 2 && (fp4 || w.size(1) == K) && q_out.size(0) == M &&
+                  q_out.size(1) == nh && N == (nh + 2 * nkv) * D,
               "skinny_gemm_qkv_rope: x [M <= 2, K], w [(nh + 2 nkv) D, K], q_out [M, nh, D]");
   const bool fp8 = check_cache(k_cache, v_cache, nkv, D);
   TORCH_CHECK(k_scale > 0 && v_scale > 0, "KV scales must be positive");
@@ -933,7 +990,11 @@ void skinny_gemm_qkv_rope(Tensor q_out, Tensor x, Tensor w, optional<Tensor> wsc
   }
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   int rc;
-  if (w.scalar_type() == at::kBFloat16) {
+  if (fp4) {
+    rc = dli::launch_skinny_gemm_fp4(nullptr, bp(x), w.data_ptr<uint8_t>(),
+                                     block_scale->data_ptr<uint8_t>(), b, (int)M, (int)N, (int)K,
+                                     cur_stream(), false, nm, &rp);
+  } else if (w.scalar_type() == at::kBFloat16) {
     rc = dli::launch_skinny_gemm(nullptr, bp(x), bp(w), b, (int)M, (int)N, (int)K, cur_stream(),
                                  false, nm, &rp);
   } else {
@@ -1016,7 +1077,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("positions"), py::arg("slot_mapping"), py::arg("cos_sin"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("nh"), py::arg("nkv"), py::arg("k_scale") = 1.0,
         py::arg("v_scale") = 1.0, py::arg("norm_w") = py::none(), py::arg("res_in") = py::none(),
-        py::arg("res_out") = py::none(), py::arg("eps") = 1e-5);
+        py::arg("res_out") = py::none(), py::arg("eps") = 1e-5,
+        py::arg("block_scale") = py::none());
+  m.def("skinny_gemm_fp4", &skinny_gemm_fp4,
+        "y = x . dequant(W4)^T (+ bias), MXFP4 weights, bf16 rows, M <= 2 (weight-streaming GEMV)",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
+        py::arg("bias") = py::none(), py::arg("swiglu") = false, py::arg("norm_w") = py::none(),
+        py::arg("res_in") = py::none(), py::arg("res_out") = py::none(), py::arg("eps") = 1e-5);
+  m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
+        py::arg("out"), py::arg("w"), py::arg("block_scale"));
   m.def("gemm4", &gemm4, "C = A . B^T, one-wave-per-SIMD 256x256 MFMA tile GEMM (gemm4.hip)",
         py::arg("out"), py::arg("a"), py::arg("b"), py::arg("splits") = 1,
         py::arg("epilogue") = 0, py::arg("grid") = 0, py::arg("a_scale") = py::none(),

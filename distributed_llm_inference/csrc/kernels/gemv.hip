@@ -381,6 +381,156 @@ __global__ void __launch_bounds__(256) skinny_gemm_fp8_kernel(const void* __rest
   gemv_store<EP, M>(v, wave, lane, N, y, rp);
 }
 
+// MXFP4 weights (OCP MX: e2m1 nibbles [N, K / 2], one e8m0 exponent per 32 consecutive k in
+// bscale [N, K / 32]): the weight stream at 17/32 byte per weight.  A lane takes 32 consecutive k
+// of a row -- one non-temporal 16-B load, exactly one scale block, so its scale is one byte load
+// -- and a wave instruction covers 2048 k.  v_cvt_scalef32_pk_bf16_fp4 widens a byte (two
+// nibbles) to a bf16 pair with the block's 2^(s - 127) as its scale operand (exact: the product
+// has at most 2 mantissa bits), v_dot2c_f32_bf16 accumulates it against the bf16 row.
+// A lane reads 64 B of x per 16 B of a weight row (four 16-B loads at a 64-B lane stride), twice
+// fp8's ratio, and with kRows = 2 rows per wave that x traffic, not HBM, set the time (measured:
+// 2.7-4.0 TB/s of weights at M = 1, M = 2 another 1.4-1.8x slower, fp8 beaten on 3 of 8 shapes:
+// profiles/mxfp4/rows2/gemv.json).  So a wave takes kFp4Pairs = 2 of the epilogues' row pairs
+// (the work of waves 2w and 2w+1 of the other kernels: gemv_row / gemv_store unchanged) and
+// every x register feeds four weight rows; kFp4Unroll = 2 k-steps of them keep the same
+// 8 x 16 B of weights (and their scale bytes) in flight per lane before any arithmetic.
+constexpr int kFp4Pairs = 2;
+constexpr int kFp4Unroll = 2;
+
+template <int M, int EP = kEpPlain, bool NORM = false>
+__global__ void __launch_bounds__(256) skinny_gemm_fp4_kernel(const bf16* __restrict__ x_in,
+                                                              const uint8_t* __restrict__ W,
+                                                              const uint8_t* __restrict__ bscale,
+                                                              const bf16* __restrict__ bias,
+                                                              bf16* __restrict__ y, int N, int K,
+                                                              GemvNorm nm, GemvRope rp) {
+  constexpr int R = kFp4Pairs * kRows;   // weight rows per wave: row q = pair q / kRows, r = q % kRows
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  const int unit0 = wave * kFp4Pairs;    // the first row pair ("wave" of gemv_row / gemv_store)
+  const int units = EP != kEpPlain ? N / 2 : (N + kRows - 1) / kRows;
+  const uint8_t* wrow[R];   // rows clamped: no load leaves W or bscale, even for idle waves
+  const uint8_t* srow[R];
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    const size_t n = (size_t)min(gemv_row<EP>(unit0 + q / kRows, q % kRows, rp), N - 1);
+    wrow[q] = W + n * (size_t)(K >> 1);
+    srow[q] = bscale + n * (size_t)(K >> 5);
+  }
+  constexpr int kStep = 64 * 32;  // elements per wave instruction
+  u32x4n wv[kFp4Unroll][R];
+  unsigned sc[kFp4Unroll][R];     // e8m0 byte of the lane's block
+  auto load_w = [&](int u, int k) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      if (k < K) {
+        wv[u][q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4n*>(wrow[q] + (k >> 1)));
+        sc[u][q] = srow[q][k >> 5];
+      } else {
+        wv[u][q] = u32x4n{0u, 0u, 0u, 0u};
+        sc[u][q] = 127u;
+      }
+    }
+  };
+  // the group issued during the norm prologue: unconditional loads (see skinny_gemm_fp8_kernel);
+  // past the row end the lane re-reads the row's last block, whose x is zero below
+  auto load_w_pre = [&](int u, int k) {
+    const int kc = k < K ? k : K - 32;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      wv[u][q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4n*>(wrow[q] + (kc >> 1)));
+      sc[u][q] = srow[q][kc >> 5];
+    }
+  };
+  const int kfirst = lane * 32;
+  if constexpr (NORM) {
+    gemv_norm_prologue<M>(x_in, nm, K, [&] {   // every thread, before any exit
+#pragma unroll
+      for (int u = 0; u < kFp4Unroll; ++u) load_w_pre(u, kfirst + u * kStep);
+    });
+  }
+  const bf16* x = NORM ? reinterpret_cast<const bf16*>(gemv_lds) : x_in;
+  if (unit0 >= units) return;
+  float acc[M][R];
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int q = 0; q < R; ++q) acc[m][q] = 0.f;
+
+  for (int k0 = kfirst; k0 < K; k0 += kStep * kFp4Unroll) {
+    const bool pre = NORM && k0 == kfirst;
+    if (!pre) {
+#pragma unroll
+      for (int u = 0; u < kFp4Unroll; ++u) load_w(u, k0 + u * kStep);
+    }
+#pragma unroll
+    for (int u = 0; u < kFp4Unroll; ++u) {
+      const int k = k0 + u * kStep;
+      bf16x8 xv[M][4];
+#pragma unroll
+      for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+          xv[m][d] = k < K ? *reinterpret_cast<const bf16x8*>(x + (size_t)m * K + k + 8 * d)
+                           : bf16x8{};
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const float s = __uint_as_float(sc[u][q] << 23);   // 2^(byte - 127), byte in [1, 254]
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {   // dword d = elements 8d .. 8d+7, byte b = (8d+2b, 8d+2b+1)
+          bf16x2 wp[4];
+          wp[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[u][q][d], s, 0);
+          wp[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[u][q][d], s, 1);
+          wp[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[u][q][d], s, 2);
+          wp[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[u][q][d], s, 3);
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+              acc[m][q] = __builtin_amdgcn_fdot2_f32_bf16(
+                  bf16x2{xv[m][d][2 * b], xv[m][d][2 * b + 1]}, wp[b], acc[m][q], false);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < kFp4Pairs; ++p) {
+    const int unit = unit0 + p;
+    float v[M][kRows];
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const int n = min(gemv_row<EP>(unit, r, rp), N - 1);
+        v[m][r] = wave_reduce_sum(acc[m][p * kRows + r]) + (bias ? (float)bias[n] : 0.f);
+      }
+    if (unit < units) gemv_store<EP, M>(v, unit, lane, N, y, rp);   // the last wave may hold one pair
+  }
+}
+
+// MXFP4 -> bf16 [N, K] for the products the GEMV does not take (they continue on the bf16
+// kernels): a thread takes one scale block per grid-stride step -- one 16-B load, one scale byte,
+// four 16-B stores.  Every output value is exact in bf16.
+__global__ void __launch_bounds__(256) dequant_mxfp4_kernel(const uint8_t* __restrict__ W,
+                                                            const uint8_t* __restrict__ bscale,
+                                                            bf16* __restrict__ out,
+                                                            size_t nblocks) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nblocks; i += stride) {
+    const u32x4n w = __builtin_nontemporal_load(reinterpret_cast<const u32x4n*>(W) + i);
+    const float s = __uint_as_float((unsigned)bscale[i] << 23);
+    bf16x8* o = reinterpret_cast<bf16x8*>(out) + i * 4;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 0);
+      const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 1);
+      const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 2);
+      const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 3);
+      o[d] = bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+    }
+  }
+}
+
 }  // namespace
 
 // swiglu: W is a swiglu_interleave'd gate|up weight [N = 2I, K], y is silu(gate) * up [M, I];
@@ -459,6 +609,52 @@ int launch_skinny_gemm_int8(bf16* y, const bf16* x, const int8_t* W, const float
   if (!gemv_rope_ok(rp, swiglu, M, N)) return -3;
   launch_fp8_m<false, true>(y, x, nullptr, reinterpret_cast<const uint8_t*>(W), wscale, bias, M,
                             N, K, swiglu, nm, rp, stream);
+  return 0;
+}
+
+template <int M, int EP>
+static void launch_fp4_t(bf16* y, const bf16* x, const uint8_t* W, const uint8_t* bscale,
+                         const bf16* bias, int N, int K, const GemvNorm* nm, const GemvRope& rp,
+                         int grid, hipStream_t stream) {
+  if (nm != nullptr)
+    skinny_gemm_fp4_kernel<M, EP, true><<<grid, 256, (size_t)M * K * 2, stream>>>(
+        x, W, bscale, bias, y, N, K, *nm, rp);
+  else
+    skinny_gemm_fp4_kernel<M, EP, false><<<grid, 256, 0, stream>>>(
+        x, W, bscale, bias, y, N, K, GemvNorm{}, rp);
+}
+
+template <int M>
+static void launch_fp4_ep(bf16* y, const bf16* x, const uint8_t* W, const uint8_t* bscale,
+                          const bf16* bias, int N, int K, int ep, const GemvNorm* nm,
+                          const GemvRope* rp, int grid, hipStream_t stream) {
+  const GemvRope r = rp ? *rp : GemvRope{};
+  if (ep == kEpRope) launch_fp4_t<M, kEpRope>(y, x, W, bscale, bias, N, K, nm, r, grid, stream);
+  else if (ep == kEpSwiGLU) launch_fp4_t<M, kEpSwiGLU>(y, x, W, bscale, bias, N, K, nm, r, grid, stream);
+  else launch_fp4_t<M, kEpPlain>(y, x, W, bscale, bias, N, K, nm, r, grid, stream);
+}
+
+int launch_skinny_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8_t* bscale,
+                           const bf16* bias, int M, int N, int K, hipStream_t stream,
+                           bool swiglu, const GemvNorm* nm, const GemvRope* rp) {
+  if (M < 1 || M > 2 || K < 32 || K % 32 != 0 || N < 1 || (swiglu && N % 32 != 0)) return -1;
+  if (!gemv_norm_ok(nm, M, K)) return -2;
+  if (!gemv_rope_ok(rp, swiglu, M, N)) return -3;
+  const int ep = gemv_ep(swiglu, rp);
+  const int units = ep != kEpPlain ? N / 2 : (N + kRows - 1) / kRows;   // row pairs
+  const int waves = (units + kFp4Pairs - 1) / kFp4Pairs;
+  const int grid = (waves + 3) / 4;
+  if (M == 1) launch_fp4_ep<1>(y, x, W, bscale, bias, N, K, ep, nm, rp, grid, stream);
+  else launch_fp4_ep<2>(y, x, W, bscale, bias, N, K, ep, nm, rp, grid, stream);
+  return 0;
+}
+
+int launch_dequant_mxfp4(bf16* out, const uint8_t* W, const uint8_t* bscale, size_t nblocks,
+                         hipStream_t stream) {
+  if (nblocks == 0) return 0;
+  const size_t want = (nblocks + 255) / 256;
+  const int grid = (int)(want < 256 * 16 ? want : 256 * 16);   // grid-stride beyond 16 per CU
+  dequant_mxfp4_kernel<<<grid, 256, 0, stream>>>(W, bscale, out, nblocks);
   return 0;
 }
 

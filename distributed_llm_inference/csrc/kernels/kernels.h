@@ -139,6 +139,15 @@ int launch_skinny_gemm_int8(bf16* y, const bf16* x, const int8_t* W, const float
 int launch_skinny_gemm(bf16* y, const bf16* x, const bf16* W, const bf16* bias, int M, int N,
                        int K, hipStream_t stream, bool swiglu = false,
                        const GemvNorm* nm = nullptr, const GemvRope* rp = nullptr);
+// MXFP4 weights: W = e2m1 nibbles [N, K / 2] (element 2j in the low nibble of byte j), bscale =
+// e8m0 block exponents [N, K / 32] (one per 32 consecutive k); bf16 rows, M <= 2, K % 32 == 0
+int launch_skinny_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8_t* bscale,
+                           const bf16* bias, int M, int N, int K, hipStream_t stream,
+                           bool swiglu = false, const GemvNorm* nm = nullptr,
+                           const GemvRope* rp = nullptr);
+// out[N, K] (bf16) = e2m1(nibble) * 2^(bscale - 127): nblocks = N * K / 32 scale blocks
+int launch_dequant_mxfp4(bf16* out, const uint8_t* W, const uint8_t* bscale, size_t nblocks,
+                         hipStream_t stream);
 // one-wave-per-SIMD 256x256 GEMM (gemm4.hip); epilogue 0 bf16, 1 fp32 partials, 2 SwiGLU,
 // 3 SwiGLU quantised to MX fp8 (precision 1; scales into out_mx), 4 bf16 partials; grid <= 0:
 // automatic persistent grid; variant < 0: default k-loop schedule.  precision 1: fp8 e4m3

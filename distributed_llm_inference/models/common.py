@@ -22,8 +22,55 @@ import torch.nn.functional as F
 from .. import ops
 
 
+class _Mxfp4Scratch:
+    """The bf16 buffers MXFP4 weights are dequantised into for the products the fp4 GEMV does not
+    take.  One flat buffer per (device, stream), sized to the largest MXFP4 weight quantised so
+    far; :meth:`reserve` (called by ``Linear.quantize_mxfp4``) is the only place that allocates,
+    so the engine's KV-pool sizing sees the buffer and a forward -- in particular one under
+    hipGraph capture -- only ever reads a pointer that already exists.  A forward on a stream
+    that never reserved one (a graph warm-up / capture stream) borrows the device's buffer and,
+    outside capture, orders itself behind the stream that used it last: reuse stays
+    stream-ordered (a captured graph is ordered by its replay stream)."""
+
+    def __init__(self):
+        self.bufs = {}   # (device index, stream id) -> flat bf16 buffer
+        self.last = {}   # buffer address -> stream that used it last
+
+    def reserve(self, device: torch.device, numel: int) -> None:
+        if device.type != "cuda":
+            return
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+        if key not in self.bufs or self.bufs[key].numel() < numel:
+            self.bufs.pop(key, None)   # the smaller one goes back to the allocator first
+            self.bufs[key] = torch.empty(numel, dtype=torch.bfloat16, device=device)
+
+    def get(self, device: torch.device, numel: int) -> torch.Tensor:
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(idx)
+        buf = self.bufs.get((idx, stream.cuda_stream))
+        if buf is None:
+            buf = next((b for (d, _), b in self.bufs.items() if d == idx), None)
+        if buf is None or buf.numel() < numel:
+            raise RuntimeError("MXFP4 dequantise scratch missing or too small: weights must be "
+                               "converted with Linear.quantize_mxfp4 on their device")
+        prev = self.last.get(buf.data_ptr())
+        if prev is None or prev.cuda_stream != stream.cuda_stream:
+            if prev is not None and not torch.cuda.is_current_stream_capturing():
+                stream.wait_stream(prev)
+            self.last[buf.data_ptr()] = stream
+        return buf
+
+    def nbytes(self, device=None) -> int:
+        return sum(b.numel() * 2 for (d, _), b in self.bufs.items()
+                   if device is None or torch.device("cuda", d) == torch.device(device))
+
+
+MXFP4_SCRATCH = _Mxfp4Scratch()
+
+
 class Linear(nn.Module):
-    """``y = x W^T (+ b)`` with W stored [out, in]; optional fp8 weights."""
+    """``y = x W^T (+ b)`` with W stored [out, in]; optional fp8 / LLM.int8 / MXFP4 weights."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False,
                  dtype: torch.dtype = torch.bfloat16, device=None):
@@ -37,6 +84,9 @@ class Linear(nn.Module):
         self.register_buffer("weight_scale", None, persistent=False)
         self.register_buffer("weight_int8", None, persistent=False)
         self.register_buffer("weight_int8_t", None, persistent=False)
+        # MXFP4: e2m1 nibbles [out, in / 2] + e8m0 block exponents [out, in / 32]
+        self.register_buffer("weight_fp4", None, persistent=False)
+        self.register_buffer("weight_block_scale", None, persistent=False)
         self.int8_threshold = 0.0
         # which projection of its layer this is ("qkv" / "o" / "gate_up" / "down", set by the
         # model): KernelPolicy.fp8_gemm4 routes fp8 products per role
@@ -49,6 +99,34 @@ class Linear(nn.Module):
     @property
     def is_int8(self) -> bool:
         return self.weight_int8 is not None
+
+    @property
+    def is_fp4(self) -> bool:
+        return self.weight_fp4 is not None
+
+    def quantize_mxfp4(self, keep_bf16: bool = False) -> None:
+        """Quantise W to MXFP4 (OCP MX: 4-bit e2m1 elements, one e8m0 scale per 32 input
+        features; ops.quantize_weight_mxfp4).  Frees the bf16 copy unless asked not to, and
+        reserves the dequantise scratch of this device / stream (see :class:`_Mxfp4Scratch`)."""
+        if self.in_features % ops.MXFP4_BLOCK:
+            raise ValueError(f"MXFP4 needs in_features % {ops.MXFP4_BLOCK} == 0, "
+                             f"got {self.in_features}")
+        self.weight_fp4, self.weight_block_scale = ops.quantize_weight_mxfp4(self.weight.data)
+        MXFP4_SCRATCH.reserve(self.weight_fp4.device, self.out_features * self.in_features)
+        if not keep_bf16:
+            self.weight = nn.Parameter(torch.empty(0, dtype=self.weight.dtype,
+                                                   device=self.weight.device), requires_grad=False)
+
+    def dense_weight(self) -> torch.Tensor:
+        """The bf16 [out, in] weight the bf16 kernels read: the parameter itself, or for MXFP4
+        weights their dequantisation (GPU: dequant_mxfp4_kernel into the persistent scratch,
+        valid until the next MXFP4 product on this stream; CPU: the torch reference)."""
+        if self.weight_fp4 is None:
+            return self.weight
+        if not self.weight_fp4.is_cuda:
+            return ops.dequantize_mxfp4(self.weight_fp4, self.weight_block_scale)
+        buf = MXFP4_SCRATCH.get(self.weight_fp4.device, self.out_features * self.in_features)
+        return ops.dequantize_mxfp4(self.weight_fp4, self.weight_block_scale, out=buf)
 
     def quantize_int8(self, threshold: float = 6.0, keep_bf16: bool = False) -> None:
         """LLM.int8 weights (reference utils/model.py:93-113, bitsandbytes ``Linear8bitLt(threshold)``):
@@ -77,7 +155,11 @@ class Linear(nn.Module):
 
     def stream_weights(self):
         """(weight, per-row scale or None, bias or None) in the format the weight-streaming
-        kernels read: bf16 [N, K], fp8 e4m3 [N, K] or int8 [N, K] with fp32 scales [N]."""
+        kernels read: bf16 [N, K], fp8 e4m3 [N, K] or int8 [N, K] with fp32 scales [N], or
+        MXFP4 nibbles [N, K / 2] with e8m0 block exponents [N, K / 32] (uint8; ``is_fp4`` tells
+        them apart)."""
+        if self.weight_fp4 is not None:
+            return self.weight_fp4, self.weight_block_scale, self.bias
         if self.weight_fp8 is not None:
             return self.weight_fp8, self.weight_scale.reshape(-1), self.bias
         if self.weight_int8 is not None:
@@ -99,6 +181,8 @@ class Linear(nn.Module):
             return False
         if swiglu and (self.bias is not None or self.out_features % 32):
             return False
+        if self.weight_fp4 is not None:
+            return bf16_rows and ops.policy().gemv
         if self.weight_int8 is not None:
             return bf16_rows and self.in_features % 16 == 0 and ops.policy().gemv
         if self.weight_fp8 is not None:
@@ -120,6 +204,9 @@ class Linear(nn.Module):
             return None
         if norm is not None and x is None:
             return None
+        if self.weight_fp4 is not None:
+            return ops.skinny_gemm_fp4(x, self.weight_fp4, self.weight_block_scale, self.bias,
+                                       swiglu=swiglu, norm=norm)
         if self.weight_int8 is not None:
             return ops.skinny_gemm_int8(x, self.weight_int8, self.weight_scale, self.bias,
                                         swiglu=swiglu, norm=norm)
@@ -144,6 +231,11 @@ class Linear(nn.Module):
                 or not self.gemv_ok(x.shape[0]) or meta.want_sink or meta.custom_mask is not None
                 or self.out_features != (nh + 2 * nkv) * head_dim):
             return None
+        if self.weight_fp4 is not None:
+            return ops.skinny_gemm_qkv_rope(x, self.weight_fp4, None, self.bias, meta.positions,
+                                            meta.slot_mapping, cos_sin, nh, nkv, head_dim,
+                                            k_cache, v_cache, meta.k_scale, meta.v_scale,
+                                            norm=norm, block_scale=self.weight_block_scale)
         if self.weight_int8 is not None:
             w, ws = self.weight_int8, self.weight_scale
         elif self.weight_fp8 is not None:
@@ -186,11 +278,17 @@ class Linear(nn.Module):
                     and x.dtype == torch.bfloat16 and x.is_contiguous()
                     and self.in_features % 8 == 0 and ops.policy().gemv):
                 # 1-2 row decode batches: weight-streaming HIP kernel (csrc/kernels/gemv.hip)
+                if self.weight_fp4 is not None:
+                    return ops.skinny_gemm_fp4(x, self.weight_fp4, self.weight_block_scale,
+                                               self.bias)
                 return ops.skinny_gemm(x, self.weight, self.bias)
+            # MXFP4: every other product dequantises into the persistent scratch and runs the
+            # bf16 path below on it, unchanged
+            w = self.dense_weight()
             sp = self.tile_splits(x)
             if sp:  # decode micro-batches: 256x256 MFMA tile kernel (csrc/kernels/gemm_tile.hip)
-                return ops.gemm_tile(x, self.weight, splits=sp, defer_reduce=defer_reduce)
-            return F.linear(x, self.weight, self.bias)
+                return ops.gemm_tile(x, w, splits=sp, defer_reduce=defer_reduce)
+            return F.linear(x, w, self.bias)
         if isinstance(x_q, ops.MxFp8):
             # MX activations from the fp8 SwiGLU epilogue: their e8m0 block scales go to the
             # block-scaled MFMA (gemm_tile.hip kFp8Mx); the MLP only hands these over when the
@@ -236,7 +334,7 @@ class Linear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in={self.in_features}, out={self.out_features}, bias={self.bias is not None}, "
-                f"fp8={self.is_fp8}, int8={self.is_int8}")
+                f"fp8={self.is_fp8}, int8={self.is_int8}, fp4={self.is_fp4}")
 
 
 @dataclass

@@ -90,6 +90,15 @@ class LlamaBlock(nn.Module):
                 lin.quantize_fp8()
         return self
 
+    def quantize_mxfp4(self) -> "LlamaBlock":
+        """MXFP4 weights (4-bit e2m1, e8m0 scale per 32 input features) for every projection."""
+        self.set_fused_swiglu(False)
+        for layer in self.layers:
+            for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj,
+                        layer.mlp.down_proj):
+                lin.quantize_mxfp4()
+        return self
+
     def new_cache(self, window_length: int = 0, num_sink_tokens: int = 0, num_blocks: int = 256,
                   block_size: int = 64) -> PartialLlamaSinkCache:
         c = PartialLlamaSinkCache(window_length, num_sink_tokens, num_blocks, block_size)

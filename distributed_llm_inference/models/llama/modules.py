@@ -166,6 +166,10 @@ class LlamaMLP(nn.Module):
                 w.weight_scale.copy_(perm(w.weight_scale.reshape(-1, 1)).reshape(w.weight_scale.shape))
                 if w.weight_int8_t is not None:
                     w.weight_int8_t.copy_(perm(w.weight_int8_t.t()).t())
+            elif w.is_fp4:
+                # per-row blocks along K: quantisation commutes with the row permutation
+                w.weight_fp4.copy_(perm(w.weight_fp4))
+                w.weight_block_scale.copy_(perm(w.weight_block_scale))
             elif w.is_fp8:
                 # per-output-channel quantisation commutes with the row permutation
                 w.weight_fp8.copy_(perm(w.weight_fp8.view(torch.uint8)).view(w.weight_fp8.dtype))
@@ -216,7 +220,7 @@ class LlamaMLP(nn.Module):
             return self.down_proj(h, defer_reduce=defer_reduce)
         if self.fused_swiglu:
             if gp.tile_splits(normed):
-                h = ops.gemm_tile(normed, gp.weight, swiglu=True)
+                h = ops.gemm_tile(normed, gp.dense_weight(), swiglu=True)
             else:
                 h = ops.swiglu_interleaved(gp(normed))
             return self.down_proj(h, defer_reduce=defer_reduce)

@@ -22,14 +22,20 @@ from .llama.model import LlamaBlock
 
 def apply_quantization(block, mode, threshold: float = 6.0):
     """Quantise a Llama / GPT-2 block in place: ``mode`` False / None / "none" (bf16), True /
-    "fp8" (e4m3 weights, per-channel scales) or "int8" (LLM.int8, outlier ``threshold``)."""
+    "fp8" (e4m3 weights, per-channel scales), "int8" (LLM.int8, outlier ``threshold``) or
+    "mxfp4" / "fp4" (OCP MX 4-bit e2m1 weights, one e8m0 scale per 32 input features)."""
     if mode in (False, None, "none", "bf16"):
         return block
     if mode is True or mode == "fp8":
         return block.quantize_fp8()
     if mode == "int8":
         return block.quantize_int8(threshold)
-    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8)")
+    if mode in ("mxfp4", "fp4"):
+        if not hasattr(block, "quantize_mxfp4"):
+            raise NotImplementedError(f"MXFP4 weights are not implemented for "
+                                      f"{type(block).__name__} (Llama-family blocks only)")
+        return block.quantize_mxfp4()
+    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4)")
 
 
 def make_block(spec: ModelSpec, layer_ids, device=None, dtype=torch.bfloat16):
@@ -81,9 +87,14 @@ class CausalLMStage(nn.Module):
         self.block.quantize_int8(threshold)
         return self
 
+    def quantize_mxfp4(self) -> "CausalLMStage":
+        apply_quantization(self.block, "mxfp4")
+        return self
+
     def quantize(self, mode, threshold: float = 6.0) -> "CausalLMStage":
         """``mode``: False / None / "none"; True / "fp8" (e4m3, the MI355X default); "int8"
-        (LLM.int8 with outlier ``threshold``)."""
+        (LLM.int8 with outlier ``threshold``); "mxfp4" / "fp4" (4-bit MX weights: the
+        interactive-decode and capacity mode; the LM head and embeddings stay bf16)."""
         apply_quantization(self.block, mode, threshold)
         return self
 

@@ -473,6 +473,76 @@ def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q, s.reshape(1, -1).contiguous()
 
 
+# MXFP4 (OCP MX v1.0): e2m1 elements, one e8m0 power-of-two scale per 32 consecutive k
+MXFP4_BLOCK = ref.MXFP4_BLOCK
+
+
+def _mxfp4_quant_rows(wf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 rows [n, K] -> (nibbles packed [n, K / 2], e8m0 bytes [n, K / 32])."""
+    n, K = wf.shape
+    b = wf.reshape(n, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = b.abs().amax(-1)
+    # e = floor(log2(amax)) - 2 (e2m1's largest binade is 2^2): frexp's exponent is floor + 1
+    e = (torch.frexp(amax)[1].to(torch.int32) - 3).clamp(-126, 127)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    inv = ((127 - e) << 23).view(torch.float32)             # 2^-e, exact
+    a = (b * inv[..., None]).abs()                          # exact: a power-of-two multiple
+    # round to nearest on {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa (torch.round is
+    # half-to-even and every binade's grid is uniform), saturating at 6
+    q = torch.where(a < 2, torch.round(a * 2) * 0.5,
+                    torch.where(a < 4, torch.round(a), torch.round(a * 0.5) * 2)).clamp_(max=6)
+    code = torch.where(q <= 2, q * 2, torch.where(q <= 4, q + 2, q * 0.5 + 4)).to(torch.uint8)
+    code = code | ((torch.signbit(b) & (code > 0)).to(torch.uint8) << 3)   # no negative zero
+    code = code.reshape(n, K // 2, 2)
+    return code[..., 0] | (code[..., 1] << 4), (e + 127).to(torch.uint8)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Offline MXFP4 quantisation of a [N, K] weight (K % 32 == 0), on ``w``'s device: returns
+    (``packed`` uint8 [N, K / 2] -- element 2j in the low nibble of byte j, torch's
+    ``float4_e2m1fn_x2`` packing -- and ``scales`` uint8 [N, K / 32], the e8m0 exponent of block
+    ``k // 32``).  Per block ``e = floor(log2(amax)) - 2`` with the stored byte ``e + 127``
+    clamped to [1, 254]; elements are ``w / 2^e`` rounded to nearest-even on the e2m1 grid,
+    saturating at +-6; an all-zero block stores byte 127.  Rows go through in chunks so the fp32
+    temporaries stay bounded.  This code is also the CPU oracle of the format."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK or w.shape[1] == 0:
+        raise ValueError(f"quantize_weight_mxfp4: [N, K] with K % {MXFP4_BLOCK} == 0, "
+                         f"got {tuple(w.shape)}")
+    N, K = w.shape
+    packed = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, K // MXFP4_BLOCK, dtype=torch.uint8, device=w.device)
+    step = max(1, (1 << 24) // K)
+    for i in range(0, N, step):
+        wf = w[i:i + step].float()
+        if not bool(torch.isfinite(wf).all()):
+            raise ValueError("quantize_weight_mxfp4: NaN or Inf in the weight")
+        packed[i:i + step], scales[i:i + step] = _mxfp4_quant_rows(wf)
+    return packed, scales
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] = ``e2m1(nibble) * 2^(scale - 127)`` (exact in bf16).  GPU: gemv.hip's
+    dequant_mxfp4_kernel into ``out`` (any contiguous bf16 buffer of at least N * K elements --
+    the persistent scratch of models/common.py -- whose first N * K elements are returned as
+    [N, K]); CPU: the torch reference."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    if not _gpu(packed):
+        r = ref.dequantize_mxfp4(packed, scales)
+        if out is None:
+            return r
+        o = out.view(-1)[:N * K].view(N, K)
+        o.copy_(r)
+        return o
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=packed.device)
+    if out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() < N * K:
+        raise ValueError("dequantize_mxfp4: out must be contiguous bf16 with >= N * K elements")
+    o = out.view(-1)[:N * K].view(N, K)
+    native().dequant_mxfp4(o, packed, scales)
+    return o
+
+
 def softmax_scale(head_dim: int) -> float:
     return 1.0 / math.sqrt(head_dim)
 
@@ -1045,21 +1115,53 @@ def skinny_gemm_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor,
     return out
 
 
+def skinny_gemm_fp4(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None, swiglu: bool = False,
+                    norm: Optional[RowNorm] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = x . dequant(packed, scales)^T (+ bias)`` for 1-2 bf16 decode rows with MXFP4 weights
+    (:func:`quantize_weight_mxfp4`'s layout): the weight stream at 17/32 byte per weight
+    (gemv.hip skinny_gemm_fp4_kernel).  ``swiglu``: the weight is a swiglu_interleave'd gate|up
+    weight, returns silu(gate) * up; ``norm``: the fused input RMSNorm."""
+    M, N = x.shape[0], packed.shape[0]
+    if not _gpu(x):
+        if norm is not None:
+            x = norm.apply(x)
+        y = x.float() @ ref.dequantize_mxfp4(packed, scales).float().t()
+        if bias is not None:
+            y = y + bias.float()
+        y = _swiglu_ref(y) if swiglu else y.to(torch.bfloat16)
+        return out.copy_(y) if out is not None else y
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=x.device)
+    native().skinny_gemm_fp4(out, x.contiguous(), packed, scales, bias, swiglu,
+                             **(norm.kwargs() if norm is not None else {}))
+    return out
+
+
 def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor],
                          bias: Optional[torch.Tensor], positions: Optional[torch.Tensor],
                          slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],
                          nh: int, nkv: int, head_dim: int, k_cache: torch.Tensor,
                          v_cache: torch.Tensor, k_scale: float = 1.0, v_scale: float = 1.0,
-                         norm: Optional[RowNorm] = None) -> torch.Tensor:
+                         norm: Optional[RowNorm] = None,
+                         block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """1-2 decode rows: the fused QKV projection (bf16, fp8 or int8 weights ``w`` [(nh + 2 nkv) D,
-    K], per-row ``w_scale`` for 8-bit) with :func:`rope_cache`'s work in the GEMV epilogue --
-    returns q [M, nh, D] rotated, k (rotated) and v written to the paged caches -- and the
-    input RMSNorm in its prologue when ``norm`` is given.  One launch instead of three."""
+    K], per-row ``w_scale`` for 8-bit; or MXFP4 nibbles [(nh + 2 nkv) D, K / 2] with their e8m0
+    ``block_scale`` [.., K / 32] -- the format is selected by passing ``block_scale``, never
+    inferred) with :func:`rope_cache`'s work in the GEMV epilogue -- returns q [M, nh, D] rotated,
+    k (rotated) and v written to the paged caches -- and the input RMSNorm in its prologue when
+    ``norm`` is given.  One launch instead of three."""
     M = x.shape[0]
+    if block_scale is not None and w_scale is not None:
+        raise ValueError("skinny_gemm_qkv_rope: block_scale (MXFP4) excludes w_scale")
     if not _gpu(x):
         if norm is not None:
             x = norm.apply(x)
-        wf = w.float() if w_scale is None else w.float() * w_scale.reshape(-1, 1)
+        if block_scale is not None:
+            wf = ref.dequantize_mxfp4(w, block_scale).float()
+        else:
+            wf = w.float() if w_scale is None else w.float() * w_scale.reshape(-1, 1)
         qkv = x.float() @ wf.t()
         if bias is not None:
             qkv = qkv + bias.float()
@@ -1071,6 +1173,7 @@ def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[tor
                                   None if w_scale is None else w_scale.reshape(-1).contiguous(),
                                   bias, positions, slot_mapping, cos_sin, k_cache, v_cache,
                                   int(nh), int(nkv), float(k_scale), float(v_scale),
+                                  block_scale=block_scale,
                                   **(norm.kwargs() if norm is not None else {}))
     return q
 

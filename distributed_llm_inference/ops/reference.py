@@ -332,3 +332,28 @@ def digest_fold(parts: torch.Tensor) -> Tuple[int, int]:
     """The digest (s1, s2) as unsigned 64-bit ints from per-workgroup partials [n, 2]."""
     p = parts.detach().cpu().tolist()
     return (sum(r[0] & _M64 for r in p) & _M64, sum(r[1] & _M64 for r in p) & _M64)
+
+
+# ----------------------------------------------------------------------------- MXFP4 weights
+MXFP4_BLOCK = 32
+# e2m1 code (3 bits) -> magnitude; the nibble's top bit is the sign
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] from MXFP4 nibbles ``packed`` uint8 [N, K / 2] (element 2j in the low nibble
+    of byte j) and e8m0 block exponents ``scales`` uint8 [N, K / 32]:
+    ``e2m1(nibble) * 2^(scale - 127)``, exact in bf16.  Rows are processed in chunks so the fp32
+    temporary stays bounded."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    out = torch.empty(N, K, dtype=torch.bfloat16, device=packed.device)
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32,
+                       device=packed.device)
+    step = max(1, (1 << 24) // max(K, 1))
+    for i in range(0, N, step):
+        p = packed[i:i + step]
+        nib = torch.stack([p & 0xF, p >> 4], dim=-1).reshape(p.shape[0], K).long()
+        s = (scales[i:i + step].to(torch.int32) << 23).view(torch.float32)   # 2^(byte - 127)
+        v = lut[nib].reshape(p.shape[0], K // MXFP4_BLOCK, MXFP4_BLOCK) * s[..., None]
+        out[i:i + step] = v.reshape(p.shape[0], K).to(torch.bfloat16)
+    return out

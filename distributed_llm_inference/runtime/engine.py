@@ -41,7 +41,8 @@ class EngineConfig:
     random_init: bool = True
     seed: int = 0
     dtype: str = "bf16"
-    quantize: object = False        # False | True / "fp8" (e4m3 weights) | "int8" (LLM.int8)
+    quantize: object = False        # False | True / "fp8" (e4m3 weights) | "int8" (LLM.int8) |
+                                    # "mxfp4" / "fp4" (4-bit MX weights)
     int8_threshold: float = 6.0     # LLM.int8 outlier threshold (quantize="int8")
     pp: int = 1
     dp: int = 1                     # pipeline replicas (world = dp x pp in init_pipeline_rank)
@@ -70,7 +71,8 @@ def build_executor(spec: ModelSpec, start: int, end: int, device: torch.device, 
     cc, sc = cfg.cache, cfg.serve
     nlayers = end - start
     if device.type == "cuda" and hasattr(stage.block, "set_fused_swiglu"):
-        # gate|up weights in the tile GEMM's SwiGLU order (bf16, or fp8 on the fp8 tile path)
+        # gate|up weights in the tile GEMM's SwiGLU order (bf16, MXFP4 rows + their block scales,
+        # or fp8 on the fp8 tile path)
         stage.block.set_fused_swiglu(True)
     if device.type == "cuda" and sc.use_graphs:
         from .gemm_tuning import tune_decode_gemms

@@ -9,7 +9,8 @@ Reference: /root/reference/distributed_llm_inference/utils/model.py —
   * B16 — weights load in bf16 (MI355X native), not fp16;
   * B10/B11 — quantisation happens only when asked (``use_quantized`` is wired through): fp8 e4m3
     with per-channel scales (CDNA4 fp8 MFMA) by default, or ``"int8"`` = LLM.int8 (int8 MFMA tile
-    GEMM + bf16 outlier columns above ``threshold``);
+    GEMM + bf16 outlier columns above ``threshold``), or ``"mxfp4"`` = OCP MX 4-bit weights
+    (quantised from bf16 at load; Llama family);
   * a random-init path builds any config without a checkpoint (``random_init=True``).
 Weights are read with ``safetensors`` (memory-mapped, no pickle execution), or -- for the
 ``pytorch_model.bin`` formats the reference also lists (utils/model.py:13) -- with
@@ -146,7 +147,8 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
                cache_dir: Optional[str] = None, token=False, device=None,
                dtype: torch.dtype = torch.bfloat16, random_init: bool = False,
                seed: int = 0) -> LlamaBlock:
-    """Build the block of ``layer_ids`` and load its weights (per layer, only the needed shards)."""
+    """Build the block of ``layer_ids`` and load its weights (per layer, only the needed shards).
+    ``use_quantized``: False, True / "fp8", "int8" or "mxfp4" (``apply_quantization``'s modes)."""
     spec = _load_config(model_name, cache_dir, token)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
     block = make_block(spec, layer_ids, device=device, dtype=dtype)
@@ -163,17 +165,19 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
 
 
 def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, device=None):
-    """Move a block to the GPU and (only if ``quantize``) convert its linears to 8-bit.
+    """Move a block to the GPU and (only if ``quantize``) convert its linears to 8 or 4 bits.
 
     ``quantize=True`` / ``"fp8"``: fp8 e4m3 weights (the MI355X-native default; enough dynamic
     range that no outlier decomposition is needed).  ``quantize="int8"``: the reference's
     LLM.int8 semantics — int8 weights, activation columns above ``threshold`` (reference default
-    5.0) computed in bf16 (reference utils/model.py:93-123).
+    5.0) computed in bf16 (reference utils/model.py:93-123).  ``quantize="mxfp4"`` (alias
+    ``"fp4"``): OCP MX 4-bit e2m1 weights with one e8m0 scale per 32 input features (17/32 byte
+    per parameter; Llama-family blocks) — the interactive-decode and capacity mode.
     """
     if device is None:
         if not torch.cuda.is_available():
             if quantize:
-                raise NotImplementedError("fp8 quantisation needs an MI355X GPU")
+                raise NotImplementedError("weight quantisation needs an MI355X GPU")
             return block
         device = torch.device("cuda", torch.cuda.current_device())
     block = block.to(device)

@@ -1,0 +1,219 @@
+#!/usr/bin/env python3
+"""MXFP4 weights measured against fp8 and bf16 on one GPU (docs/kernels.md quotes the results).
+
+    python3 scripts/bench_mxfp4.py [all|gemv|decode|batch512] [--num-layers N] [--out DIR]
+
+``gemv``      per-shape weight-streaming GEMV time for the four Llama-3-70B projections at
+              M = 1 and 2, fp4 / fp8 / bf16: every format's launches captured in one hipGraph
+              over enough weight copies (> 1 GiB) that they stream from HBM, replays of the three
+              formats interleaved on the same box; us per launch and effective weight TB/s.
+``decode``    batch-1 decode through LLMEngine (random-init llama-3-70b, ``--num-layers`` of its
+              80 layers): ms per token and KV blocks for bf16, fp8 and mxfp4.
+``batch512``  one 512-sequence decode step, mxfp4 against bf16: the price of the dequantise pass.
+``all``       (default) runs the three steps one after the other, each as a child process under
+              its own time limit; it stops at the first step that fails and never opens the GPU
+              itself.  Results: ``<out>/gemv.json``, ``decode_b1.json``, ``decode_b512.json``.
+"""
+import argparse
+import gc
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+STEP_LIMIT_S = {"gemv": 300, "decode": 900, "batch512": 600}
+H, I = 8192, 28672
+SHAPES = {"qkv": (10240, H), "o": (H, H), "gate_up": (2 * I, H), "down": (H, I)}
+BYTES_PER_WEIGHT = {"fp4": 17 / 32, "fp8": 1.0, "bf16": 2.0}
+
+
+def _torch():
+    import torch
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_mxfp4: needs a GPU (nothing is measured without one)")
+    return torch
+
+
+# ----------------------------------------------------------------------------- GEMV rates
+def step_gemv(a):
+    torch = _torch()
+    from distributed_llm_inference import ops
+    dev = torch.device("cuda", 0)
+
+    def weights(fmt, N, K, n):
+        if fmt == "bf16":
+            return [(torch.empty(N, K, device=dev, dtype=torch.bfloat16).normal_(0, 0.02),)
+                    for _ in range(n)]
+        if fmt == "fp8":
+            sc = torch.rand(N, device=dev) * 1e-2 + 1e-3
+            return [(torch.randint(-100, 100, (N, K), device=dev, dtype=torch.int8)
+                     .view(torch.uint8).bitwise_and_(0x77).view(torch.float8_e4m3fn), sc)
+                    for _ in range(n)]
+        return [(torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8),
+                 torch.randint(117, 128, (N, K // 32), device=dev, dtype=torch.uint8))
+                for _ in range(n)]
+
+    def call(fmt, x, w):
+        if fmt == "bf16":
+            return ops.skinny_gemm(x, w[0])
+        if fmt == "fp8":
+            return ops.skinny_gemm_fp8(x, w[0], w[1])
+        return ops.skinny_gemm_fp4(x, w[0], w[1])
+
+    def graph(fns):
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            for f in fns:
+                f()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for f in fns:
+                f()
+        g.replay()
+        torch.cuda.synchronize()
+        return g
+
+    def timed(g, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps     # us per replay
+
+    res = {"unit": "us per launch (median of interleaved rounds), effective weight TB/s",
+           "bytes_per_weight": BYTES_PER_WEIGHT, "shapes": {}}
+    for name, (N, K) in SHAPES.items():
+        for M in (1, 2):
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+            graphs, copies = {}, {}
+            for fmt in ("fp4", "fp8", "bf16"):
+                wbytes = N * K * BYTES_PER_WEIGHT[fmt]
+                n = int(min(48, max(3, -(-(1 << 30) // int(wbytes)))))
+                ws = weights(fmt, N, K, n)
+                graphs[fmt] = (graph([(lambda w=w: call(fmt, x, w)) for w in ws]), ws)
+                copies[fmt] = n
+            samples = {fmt: [] for fmt in graphs}
+            for _ in range(7):                       # interleaved: same box, same minute
+                for fmt, (g, _) in graphs.items():
+                    samples[fmt].append(timed(g, 10) / copies[fmt])
+            row = {}
+            for fmt in graphs:
+                us = statistics.median(samples[fmt])
+                row[fmt] = {"us": round(us, 2),
+                            "TBps": round(N * K * BYTES_PER_WEIGHT[fmt] / us / 1e6, 2),
+                            "min_us": round(min(samples[fmt]), 2),
+                            "max_us": round(max(samples[fmt]), 2), "copies": copies[fmt]}
+            row["fp4_vs_fp8"] = round(row["fp4"]["us"] / row["fp8"]["us"], 3)
+            res["shapes"][f"{name}_M{M}"] = dict(N=N, K=K, M=M, **row)
+            print(f"{name:8s} M={M} " + "  ".join(
+                f"{f} {row[f]['us']:8.2f} us {row[f]['TBps']:5.2f} TB/s" for f in graphs)
+                + f"  fp4/fp8 {row['fp4_vs_fp8']:.3f}", flush=True)
+            del graphs
+            torch.cuda.empty_cache()
+    return res
+
+
+# ----------------------------------------------------------------------------- engine decode
+def _decode_ms(a, quantize, batch, short, long_):
+    """ms per decode step of ``batch`` sequences: two generate() calls that differ only in the
+    number of decode steps (the prefill and the start-up cancel in the difference)."""
+    torch = _torch()
+    from distributed_llm_inference.config import CacheConfig, ServeConfig, resolve_model
+    from distributed_llm_inference.runtime.engine import EngineConfig, LLMEngine
+    from distributed_llm_inference.runtime.sequence import SamplingParams
+    spec = resolve_model("llama-3-70b")
+    if a.num_layers:
+        spec = spec.replace(num_layers=a.num_layers, name=f"{spec.name}-{a.num_layers}L")
+    cfg = EngineConfig(model=spec, random_init=True, seed=0, quantize=quantize,
+                       cache=CacheConfig(block_size=64, gpu_memory_utilization=0.90),
+                       serve=ServeConfig(max_batch_size=batch, max_num_batched_tokens=2048,
+                                         max_seq_len=512, use_graphs=True,
+                                         graph_batch_sizes=[batch]))
+    eng = LLMEngine(spec, device="cuda:0", cfg=cfg)
+    blocks = min(ex.pool.num_blocks for ex in eng.executors)
+    prompts = [[(7 * i + j) % 1000 + 1 for j in range(4)] for i in range(batch)]
+
+    def run(n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = eng.generate(prompts, SamplingParams(max_tokens=n, ignore_eos=True))
+        torch.cuda.synchronize()
+        assert all(len(s.output) == n for s in out)
+        return time.perf_counter() - t0
+
+    run(short)                                        # warm-up: code objects, graphs
+    ms = [(run(long_) - run(short)) / (long_ - short) * 1e3 for _ in range(3)]
+    del eng
+    gc.collect()
+    torch.cuda.empty_cache()
+    return {"ms_per_step": round(statistics.median(ms), 3), "samples_ms": [round(m, 3) for m in ms],
+            "kv_blocks": int(blocks), "layers": spec.num_layers}
+
+
+def step_decode(a):
+    res = {"model": "llama-3-70b (random init)", "batch": 1, "num_layers": a.num_layers or 80,
+           "unit": "ms per token (difference of two generate() calls), KV blocks of 64 tokens"}
+    for mode in ("mxfp4", "fp8", "bf16"):
+        print(f"batch 1, {mode}: building the engine", flush=True)
+        res[mode] = _decode_ms(a, False if mode == "bf16" else mode, 1, 16, 144)
+        print(mode, res[mode], flush=True)
+        _save(a, "decode_b1.json", res)           # what is measured so far survives a time limit
+    return res
+
+
+def step_batch512(a):
+    res = {"model": "llama-3-70b (random init)", "batch": 512, "num_layers": a.num_layers or 80,
+           "unit": "ms per 512-sequence decode step (difference of two generate() calls)"}
+    for mode in ("mxfp4", "bf16"):
+        print(f"batch 512, {mode}: building the engine", flush=True)
+        res[mode] = _decode_ms(a, False if mode == "bf16" else mode, 512, 4, 28)
+        print(mode, res[mode], flush=True)
+        _save(a, "decode_b512.json", res)
+    res["mxfp4_vs_bf16"] = round(res["mxfp4"]["ms_per_step"] / res["bf16"]["ms_per_step"], 3)
+    return res
+
+
+def _save(a, name, res):
+    with open(os.path.join(a.out, name), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+STEPS = {"gemv": (step_gemv, "gemv.json"), "decode": (step_decode, "decode_b1.json"),
+         "batch512": (step_batch512, "decode_b512.json")}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("step", nargs="?", default="all", choices=["all"] + list(STEPS))
+    ap.add_argument("--num-layers", type=int, default=0,
+                    help="decode / batch512: this many of the model's 80 layers (0 = all)")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "mxfp4"))
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    if a.step == "all":
+        for step in STEPS:
+            cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S[step]), sys.executable,
+                   os.path.abspath(__file__), step, "--num-layers", str(a.num_layers),
+                   "--out", a.out]
+            rc = subprocess.run(cmd).returncode
+            if rc != 0:
+                print(f"bench_mxfp4: step {step} ended with status {rc}; stopping", flush=True)
+                return rc
+        return 0
+    fn, name = STEPS[a.step]
+    _save(a, name, fn(a))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
