@@ -445,6 +445,11 @@ class KernelPolicy:
     # rows per wave, 64-key steps) wherever it applies (bf16 full cache, head_dim 128, any GQA
     # group incl. MHA, no custom mask); else attention.hip's 16x16x32 kernel
     prefill_m32: bool = True
+    # MXFP4 weights: products of more than 2 rows on the MFMA-native fp4 x fp8 tile GEMM
+    # (csrc/kernels/gemm_fp4.hip; activations quantised to MX fp8 first) instead of dequantising
+    # the weight to bf16.  Experimental and off: it changes the numerics of those products (fp8
+    # activation rounding; docs/kernels.md "MXFP4 weights")
+    fp4_mfma: bool = False
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 

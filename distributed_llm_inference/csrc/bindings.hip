@@ -928,6 +928,67 @@ void dequant_mxfp4(Tensor out, Tensor w, Tensor bscale) {
            "dequant_mxfp4");
 }
 
+// MX fp8 quantiser: bf16 x [M, K] (K % 128 == 0) -> e4m3 bytes q [M, K] + e8m0 scales sc
+// [K / 128 * ceil(M / 64) * 64] in gemm_tile.hip's mx_off layout (ops.mx_quantize's rule)
+void quant_mx(Tensor q, Tensor sc, Tensor x) {
+  CHECK_IN(q); CHECK_IN(sc); CHECK_IN(x); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2, "quant_mx: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M <= (1 << 24) && K >= 128 && K % 128 == 0 && K <= (1 << 24),
+              "quant_mx: x [M, K] with M >= 1 and K % 128 == 0");
+  TORCH_CHECK(q.element_size() == 1 && q.size(0) == M && q.size(1) == K,
+              "quant_mx: q = 1-byte [M, K]");
+  TORCH_CHECK(sc.element_size() == 1 && sc.numel() == (K / 128) * ((M + 63) / 64) * 64,
+              "quant_mx: sc = [K / 128][ceil(M / 64) * 64] bytes");
+  TORCH_CHECK(q.device() == x.device() && sc.device() == x.device(), "quant_mx: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_quant_mx(static_cast<uint8_t*>(q.data_ptr()),
+                                static_cast<uint8_t*>(sc.data_ptr()), bp(x), (int)M, (int)K,
+                                cur_stream()),
+           "quant_mx");
+}
+
+// MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip).
+// epilogue 0: out bf16 [M, N] (splits > 1 needs an fp32 workspace of splits * M * N); 1: the fp32
+// split-K slabs only, into workspace (out unused); 2: SwiGLU, out bf16 [M, N / 2] (splits == 1)
+void gemm_fp4(Tensor out, Tensor a_q, Tensor a_mx, Tensor w, Tensor bscale, int64_t splits,
+              int64_t epilogue, optional<Tensor> workspace) {
+  CHECK_IN(out); CHECK_IN(a_q); CHECK_IN(a_mx); CHECK_BF16(out);
+  TORCH_CHECK(a_q.dim() == 2 && a_q.element_size() == 1, "gemm_fp4: a_q = e4m3 bytes [M, K]");
+  const int64_t M = a_q.size(0), K = a_q.size(1);
+  TORCH_CHECK(M >= 1 && M <= (1 << 20) && K >= 128 && K % 128 == 0 && K <= (1 << 24),
+              "gemm_fp4: needs M >= 1 and K % 128 == 0");
+  check_mxfp4(w, bscale, K, "gemm_fp4");
+  const int64_t N = w.size(0), kt = K / 128;
+  TORCH_CHECK(N >= 256 && N % 256 == 0 && N <= (1 << 24), "gemm_fp4: needs N % 256 == 0");
+  TORCH_CHECK(a_mx.element_size() == 1 && a_mx.numel() == kt * ((M + 63) / 64) * 64,
+              "gemm_fp4: a_mx = a_q's e8m0 scales [K / 128][ceil(M / 64) * 64]");
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 2,
+              "gemm_fp4: epilogue must be 0 (store), 1 (split-K partials only) or 2 (swiglu)");
+  TORCH_CHECK(splits >= 1 && splits <= kt, "gemm_fp4: 1 <= splits <= k-tiles");
+  TORCH_CHECK((epilogue == 1) == (splits > 1) || epilogue == 0,
+              "gemm_fp4: epilogue 1 needs splits > 1, epilogue 2 splits == 1");
+  TORCH_CHECK(a_q.device() == w.device() && a_mx.device() == w.device() &&
+                  out.device() == w.device(), "gemm_fp4: one device");
+  if (epilogue != 1)
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == (epilogue == 2 ? N / 2 : N),
+                "gemm_fp4: output shape");
+  float* ws = nullptr;
+  if (splits > 1) {
+    TORCH_CHECK(workspace.has_value(), "gemm_fp4: split-K needs a workspace");
+    CHECK_IN(*workspace); CHECK_F32(*workspace);
+    TORCH_CHECK(workspace->numel() >= splits * M * N && workspace->device() == w.device(),
+                "gemm_fp4: workspace too small");
+    ws = workspace->data_ptr<float>();
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  check_rc(dli::launch_gemm_fp4(out.data_ptr(), static_cast<const uint8_t*>(a_q.data_ptr()),
+                                static_cast<const uint8_t*>(a_mx.data_ptr()),
+                                w.data_ptr<uint8_t>(), bscale.data_ptr<uint8_t>(), ws, (int)M,
+                                (int)N, (int)K, (int)splits, (int)epilogue, cur_stream()),
+           "gemm_fp4");
+}
+
 // 1-2 decode rows: the fused QKV GEMV whose epilogue does rope_cache's work (q rotated into q_out,
 // k rotated and v written into the paged caches), optionally with the fused input RMSNorm.
 // w: bf16 [N, K], fp8 e4m3 / int8 [N, K] with fp32 per-row wscale, or (block_scale given) MXFP4
@@ -1086,6 +1147,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("res_in") = py::none(), py::arg("res_out") = py::none(), py::arg("eps") = 1e-5);
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
         py::arg("out"), py::arg("w"), py::arg("block_scale"));
+  m.def("quant_mx", &quant_mx, "MX fp8 quantiser: bf16 [M, K] -> e4m3 bytes + e8m0 per (row, 128)",
+        py::arg("q"), py::arg("sc"), py::arg("x"));
+  m.def("gemm_fp4", &gemm_fp4,
+        "C = A . W^T, MX fp8 activations x MXFP4 weights on the mixed-format block-scaled MFMA",
+        py::arg("out"), py::arg("a_q"), py::arg("a_mx"), py::arg("w"), py::arg("block_scale"),
+        py::arg("splits") = 1, py::arg("epilogue") = 0, py::arg("workspace") = py::none());
+  m.def("gemm_fp4_max_ktiles", []() { return dli::gemm_fp4_max_ktiles(); },
+        "k-tiles (of 128) one split of gemm_fp4 may own");
   m.def("gemm4", &gemm4, "C = A . B^T, one-wave-per-SIMD 256x256 MFMA tile GEMM (gemm4.hip)",
         py::arg("out"), py::arg("a"), py::arg("b"), py::arg("splits") = 1,
         py::arg("epilogue") = 0, py::arg("grid") = 0, py::arg("a_scale") = py::none(),

@@ -148,6 +148,20 @@ int launch_skinny_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8
 // out[N, K] (bf16) = e2m1(nibble) * 2^(bscale - 127): nblocks = N * K / 32 scale blocks
 int launch_dequant_mxfp4(bf16* out, const uint8_t* W, const uint8_t* bscale, size_t nblocks,
                          hipStream_t stream);
+// MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip):
+// C[M, N] = (e4m3(a_q) * 2^(a_mx - 127)) . (e2m1(W) * 2^(bscale - 127))^T, fp32 accumulation.
+// a_q [M, K] bytes, a_mx in mx_off layout (launch_quant_mx), W / bscale as above; N % 256 == 0,
+// K % 128 == 0, any M >= 1.  epilogue 0: bf16 C [M, N] (splits > 1: fp32 slabs in `workspace`
+// [splits][M * N], reduced here); 1: the slabs only (splits > 1, C unused); 2: SwiGLU on
+// swiglu_interleave'd weight rows, bf16 C [M, N / 2] (splits == 1).  Every split owns >= 1 k-tile
+// and at most gemm_fp4_max_ktiles() of them.
+int launch_gemm_fp4(void* C, const uint8_t* a_q, const uint8_t* a_mx, const uint8_t* W,
+                    const uint8_t* bscale, float* workspace, int M, int N, int K, int splits,
+                    int epilogue, hipStream_t stream);
+int gemm_fp4_max_ktiles();
+// bf16 rows [rows, K] (K % 128 == 0) -> e4m3 bytes q [rows, K] + e8m0 scales sc (mx_off layout,
+// K / 128 * ceil(rows / 64) * 64 bytes; rows past `rows` hold 127): ops.mx_quantize's rule
+int launch_quant_mx(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K, hipStream_t stream);
 // one-wave-per-SIMD 256x256 GEMM (gemm4.hip); epilogue 0 bf16, 1 fp32 partials, 2 SwiGLU,
 // 3 SwiGLU quantised to MX fp8 (precision 1; scales into out_mx), 4 bf16 partials; grid <= 0:
 // automatic persistent grid; variant < 0: default k-loop schedule.  precision 1: fp8 e4m3

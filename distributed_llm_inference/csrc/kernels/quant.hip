@@ -272,4 +272,47 @@ int launch_silu_mul_quant(uint8_t* q, float* scale, const bf16* x, int rows, int
   return 0;
 }
 
+// MX fp8 activations for the block-scaled MFMA (gemm_fp4.hip): bf16 rows [rows, K] -> e4m3 bytes
+// [rows, K] + one e8m0 byte per (row, 128-column block) in common.h's mx_off layout, by
+// ops.mx_quantize's rule (mx_exponent); the rows [rows, 64 nb) of the scale array get 127.
+// 16 lanes per block, 8 values (16 bytes in, 8 bytes out) per lane; blocks are numbered row-major
+// so a wave reads 512 contiguous bytes.
+__global__ void __launch_bounds__(256) quant_mx_kernel(uint8_t* __restrict__ q,
+                                                       uint8_t* __restrict__ sc,
+                                                       const bf16* __restrict__ x, int rows,
+                                                       int nkb, int nb) {
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int pad = nb * 64 - rows;
+  for (size_t i = gid; i < (size_t)pad * nkb; i += (size_t)gridDim.x * 256)
+    sc[mx_off((int)(i / pad), rows + (int)(i % pad), nb)] = 127;
+  const size_t blk = gid >> 4;
+  if (blk >= (size_t)rows * nkb) return;   // whole 16-lane groups leave together
+  const int sub = (int)(gid & 15);
+  const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + blk * 128 + sub * 8);
+  float f[8], a = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f[j] = (float)v[j];
+    a = fmaxf(a, fabsf(f[j]));
+  }
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+  const int k = mx_exponent(a);
+  const float inv = mx_inv_scale(k);
+  uint2 o;
+  o.x = pack4_fp8(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
+  o.y = pack4_fp8(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
+  *reinterpret_cast<uint2*>(q + blk * 128 + sub * 8) = o;
+  if (sub == 0) sc[mx_off((int)(blk % nkb), (int)(blk / nkb), nb)] = (uint8_t)(k + 127);
+}
+
+int launch_quant_mx(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K, hipStream_t stream) {
+  if (rows < 1 || K < 128 || K % 128 != 0) return -1;
+  const int nkb = K / 128, nb = (rows + 63) / 64;
+  const size_t threads = (size_t)rows * nkb * 16;
+  if ((threads + 255) / 256 > 0x7fffffffULL) return -1;
+  quant_mx_kernel<<<(int)((threads + 255) / 256), 256, 0, stream>>>(q, sc, x, rows, nkb, nb);
+  return 0;
+}
+
 }  // namespace dli

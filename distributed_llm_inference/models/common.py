@@ -174,6 +174,20 @@ class Linear(nn.Module):
             return 0
         return ops.tile_gemm_splits(x.shape[0], self.out_features, self.in_features)
 
+    def fp4_mfma_ok(self, x: Optional[torch.Tensor]) -> bool:
+        """Whether the product of ``x`` with these MXFP4 weights runs on the MFMA-native fp4 tile
+        GEMM (``KernelPolicy.fp4_mfma``; ops.gemm_fp4_mx on MX-quantised rows) instead of the
+        dequantise path.  Shapes and policy only, never the device: the CPU takes the same
+        branch, so its torch arithmetic is the oracle of the GPU kernels."""
+        if (self.weight_fp4 is None or not ops.policy().fp4_mfma or x is None or x.dim() != 2
+                or self.in_features % 128 or self.out_features % 256):
+            return False
+        rows = x.shape[0]
+        if rows < 1 or (rows <= ops.SKINNY_DISPATCH_M and ops.policy().gemv):
+            return False   # 1-2 decode rows stay on the weight-streaming GEMV
+        max_m = ops.policy().tile_gemm_max_m
+        return max_m == 0 or rows <= max_m
+
     def gemv_ok(self, rows: int, swiglu: bool = False, bf16_rows: bool = True) -> bool:
         """Whether :meth:`gemv` takes a product of ``rows`` GPU rows (bf16 rows, or with
         ``bf16_rows=False`` the fused quantiser's fp8 rows for fp8 weights)."""
@@ -272,6 +286,14 @@ class Linear(nn.Module):
             if isinstance(y, ops.SplitKPartials):   # the consumer reduces (rms_norm / rope_cache)
                 return y
             y = y.reshape(*x.shape[:-1], self.out_features)
+            return y + self.bias if self.bias is not None else y
+        if self.fp4_mfma_ok(x):
+            # MXFP4 weights, more than 2 rows: rows quantised to MX fp8, then the fp4 x fp8
+            # block-scaled MFMA tile GEMM (csrc/kernels/gemm_fp4.hip) -- no dequantised weight
+            sp = ops.tile_gemm_splits_fp4(x.shape[0], self.out_features, self.in_features)
+            y = ops.gemm_fp4_mx(ops.quant_mx(x), self.weight_fp4, self.weight_block_scale, sp,
+                                defer_reduce=(defer_reduce and self.bias is None
+                                              and sp <= ops.TILE_MAX_SPLITS))
             return y + self.bias if self.bias is not None else y
         if self.weight_fp8 is None:
             if (x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= ops.SKINNY_DISPATCH_M

@@ -218,6 +218,14 @@ class LlamaMLP(nn.Module):
             else:
                 h = ops.swiglu_interleaved(gp(None, (xq, xs)))
             return self.down_proj(h, defer_reduce=defer_reduce)
+        if self.fused_swiglu and gp.fp4_mfma_ok(normed):
+            # MXFP4 on the fp4 x fp8 MFMA tile GEMM (KernelPolicy.fp4_mfma), SwiGLU in its epilogue
+            if gp.in_features // 128 <= ops.FP4_MAX_KTILES:
+                h = ops.gemm_fp4_mx(ops.quant_mx(normed), gp.weight_fp4, gp.weight_block_scale,
+                                    swiglu=True)
+            else:   # K past the whole-K kernel's scale slot: split-K product, SwiGLU after it
+                h = ops.swiglu_interleaved(gp(normed))
+            return self.down_proj(h, defer_reduce=defer_reduce)
         if self.fused_swiglu:
             if gp.tile_splits(normed):
                 h = ops.gemm_tile(normed, gp.dense_weight(), swiglu=True)

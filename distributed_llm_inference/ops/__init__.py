@@ -972,6 +972,87 @@ def mx_quantize(h: torch.Tensor) -> MxFp8:
     return MxFp8(q, sc.view(-1))
 
 
+def quant_mx(h: torch.Tensor) -> MxFp8:
+    """:func:`mx_quantize` of bf16 rows [M, K] (K % 128 == 0) for the block-scaled MFMA's
+    activation operand: on the GPU the hand-written quantiser (quant.hip quant_mx_kernel,
+    bit-identical to the torch rule, which stays the CPU path and the oracle)."""
+    if not _gpu(h):
+        return mx_quantize(h)
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.shape[1] % 128 or h.shape[0] < 1:
+        raise ValueError(f"quant_mx: bf16 [M, K] with K % 128 == 0, got {tuple(h.shape)} {h.dtype}")
+    M, K = h.shape
+    q = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=h.device)
+    sc = torch.empty(K // 128 * ((M + 63) // 64) * 64, dtype=torch.uint8, device=h.device)
+    native().quant_mx(q, sc, h.contiguous())
+    return MxFp8(q, sc)
+
+
+FP4_MAX_KTILES = 128  # k-tiles one split of gemm_fp4 may own (gemm_fp4.hip kMaxKt: its LDS slot)
+
+
+def gemm_fp4_mx(a: MxFp8, packed: torch.Tensor, scales: torch.Tensor, splits: int = 1,
+                swiglu: bool = False, defer_reduce: bool = False,
+                out: Optional[torch.Tensor] = None):
+    """MXFP4 weights x MX fp8 activations: ``(q * 2^e) @ dequant(packed, scales)^T`` -> bf16 [M, N],
+    both scale sets applied by the mixed-format block-scaled MFMA itself (gemm_fp4.hip; fp32
+    accumulation, no dequantised copy of the weight).  N % 256 == 0, K % 128 == 0, any M.
+    ``swiglu``: the weight rows are in swiglu_interleave order and silu(gate) * up [M, N / 2] is
+    returned.  ``defer_reduce`` (split-K): return the fp32 partials as :class:`SplitKPartials`.
+    CPU: the product of the two dequantised operands (the oracle of the GPU path)."""
+    M, K = a.q.shape
+    N = packed.shape[0]
+    splits = max(1, int(splits))
+    if not _gpu(a.q):
+        y = (a.dequantize() @ ref.dequantize_mxfp4(packed, scales).float().t()).to(torch.bfloat16)
+        if swiglu:
+            return swiglu_interleaved(y, out)
+        return out.copy_(y) if out is not None else y
+    kt = K // 128
+    if N % 256 or K % 128 or packed.shape[1] * 2 != K:
+        raise ValueError(f"gemm_fp4_mx: needs N % 256 == 0 and K % 128 == 0, got N={N} K={K}")
+    if splits > kt or (splits - 1) * (-(-kt // splits)) >= kt or -(-kt // splits) > FP4_MAX_KTILES:
+        raise ValueError(f"gemm_fp4_mx: K={K} does not split {splits} ways (every split owns 1 to "
+                         f"{FP4_MAX_KTILES} k-tiles of 128)")
+    if swiglu and splits > 1:
+        raise ValueError("gemm_fp4_mx: fused SwiGLU takes whole-K tiles (splits = 1)")
+    dev = a.q.device
+    if splits > 1 and defer_reduce and policy().defer_splitk:
+        parts = torch.empty(splits, M, N, dtype=torch.float32, device=dev)
+        dummy = torch.empty(M, 0, dtype=torch.bfloat16, device=dev)   # C is unused
+        native().gemm_fp4(dummy, a.q, a.sc, packed, scales, splits, 1, parts.view(-1))
+        return SplitKPartials(parts)
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=dev)
+    workspace = torch.empty(splits * M * N, dtype=torch.float32, device=dev) if splits > 1 else None
+    native().gemm_fp4(out, a.q, a.sc, packed, scales, splits, 2 if swiglu else 0, workspace)
+    return out
+
+
+def tile_gemm_splits_fp4(M: int, N: int, K: int) -> int:
+    """Split-K factor for :func:`gemm_fp4_mx` (always >= 1: the kernel takes any M).
+    :func:`tile_gemm_splits_fp8`'s rule -- fill the 256 CUs with whole waves of 256 x 256 tiles,
+    ties to fewer splits -- without its hand-over of small M to the library (there is no library
+    fp4 product), and with every split inside the kernel's LDS scale slot."""
+    k_tiles = K // 128
+    tiles = ((M + 255) // 256) * (N // 256)
+    best, best_util = 0, 0.0
+    for s in range(1, TILE_MAX_SPLITS + 1):
+        if s > k_tiles or (s > 1 and tiles * s > 2 * _CUS):
+            break
+        kps = -(-k_tiles // s)
+        if (s - 1) * kps >= k_tiles or kps > FP4_MAX_KTILES:
+            continue
+        work = tiles * s
+        util = work / (_CUS * ((work + _CUS - 1) // _CUS))
+        if util > best_util + 1e-9:
+            best, best_util = s, util
+    if best == 0:   # very long K on a full grid: the fewest splits that fit the scale slot
+        best = -(-k_tiles // FP4_MAX_KTILES)
+        while (best - 1) * (-(-k_tiles // best)) >= k_tiles:
+            best += 1
+    return best
+
+
 MX_MAX_KTILES = 64   # k-tiles of scales one kFp8Mx workgroup keeps in LDS (gemm_tile.hip kMxMaxKt)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MXFP4 weights measured against fp8 and bf16 on one GPU (docs/kernels.md quotes the results).
 
-    python3 scripts/bench_mxfp4.py [all|gemv|decode|batch512] [--num-layers N] [--out DIR]
+    python3 scripts/bench_mxfp4.py [all|gemv|gemm|decode|batch512] [--num-layers N] [--out DIR]
 
 ``gemv``      per-shape weight-streaming GEMV time for the four Llama-3-70B projections at
               M = 1 and 2, fp4 / fp8 / bf16: every format's launches captured in one hipGraph
@@ -9,10 +9,16 @@
               formats interleaved on the same box; us per launch and effective weight TB/s.
 ``decode``    batch-1 decode through LLMEngine (random-init llama-3-70b, ``--num-layers`` of its
               80 layers): ms per token and KV blocks for bf16, fp8 and mxfp4.
-``batch512``  one 512-sequence decode step, mxfp4 against bf16: the price of the dequantise pass.
-``all``       (default) runs the three steps one after the other, each as a child process under
+``gemm``      the four projections at M = 64 and 512 through ``Linear``: MXFP4 on the fp4 x fp8
+              MFMA tile GEMM (``KernelPolicy.fp4_mfma``; with and without its activation
+              quantiser) against the dequantise path, fp8 and bf16; graph-timed over weight
+              copies, candidates interleaved, median of 7 rounds.
+``batch512``  one 512-sequence decode step, mxfp4 against bf16: the price of the dequantise pass;
+              then mxfp4 with ``fp4_mfma`` on and off (and fp8) in the same process.
+``all``       (default) runs the steps one after the other, each as a child process under
               its own time limit; it stops at the first step that fails and never opens the GPU
-              itself.  Results: ``<out>/gemv.json``, ``decode_b1.json``, ``decode_b512.json``.
+              itself.  Results: ``<out>/gemv.json``, ``gemm.json``, ``decode_b1.json``,
+              ``decode_b512.json``, ``decode_b512_mfma.json``.
 """
 import argparse
 import gc
@@ -26,7 +32,7 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-STEP_LIMIT_S = {"gemv": 300, "decode": 900, "batch512": 600}
+STEP_LIMIT_S = {"gemv": 300, "gemm": 420, "decode": 900, "batch512": 900}
 H, I = 8192, 28672
 SHAPES = {"qkv": (10240, H), "o": (H, H), "gate_up": (2 * I, H), "down": (H, I)}
 BYTES_PER_WEIGHT = {"fp4": 17 / 32, "fp8": 1.0, "bf16": 2.0}
@@ -122,18 +128,121 @@ def step_gemv(a):
     return res
 
 
+# ----------------------------------------------------------------------------- tile GEMM
+def step_gemm(a):
+    """us per product of ``Linear.forward`` (what a decode step pays, activation preparation
+    included) per weight format; ``fp4_mfma_gemm`` is the fp4 kernel alone on rows quantised
+    outside the timed graph."""
+    import copy
+    torch = _torch()
+    from distributed_llm_inference import ops
+    from distributed_llm_inference.models.common import Linear
+    dev = torch.device("cuda", 0)
+    cands = ("fp4_mfma", "fp4_mfma_gemm", "fp4_dequant", "fp8", "bf16")
+    wfmt = {"fp4_mfma": "fp4", "fp4_mfma_gemm": "fp4", "fp4_dequant": "fp4", "fp8": "fp8",
+            "bf16": "bf16"}
+
+    def linears(fmt, N, K, n):
+        base = Linear(K, N, device=dev)
+        base.weight.data.normal_(0, 0.02)
+        if fmt == "fp4":
+            base.quantize_mxfp4()
+        elif fmt == "fp8":
+            base.quantize_fp8()
+        return [base] + [copy.deepcopy(base) for _ in range(n - 1)]
+
+    def graph(fns):
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            for f in fns:
+                f()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for f in fns:
+                f()
+        g.replay()
+        torch.cuda.synchronize()
+        return g
+
+    def timed(g, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps     # us per replay
+
+    res = {"unit": "us per product (median of 7 interleaved rounds), dense TFLOP/s",
+           "candidates": {"fp4_mfma": "MXFP4 Linear, fp4_mfma=1: MX quantiser + gemm_fp4 (+ reduce)",
+                          "fp4_mfma_gemm": "gemm_fp4 (+ reduce) alone, rows quantised beforehand",
+                          "fp4_dequant": "MXFP4 Linear, fp4_mfma=0: dequantise + the bf16 path",
+                          "fp8": "fp8 Linear: row quantiser + fp8 GEMM", "bf16": "bf16 Linear"},
+           "shapes": {}}
+    for name, (N, K) in SHAPES.items():
+        lins = {}
+        for fmt in ("fp4", "fp8", "bf16"):
+            # enough copies that the weights stream from HBM (> 512 MiB per replay)
+            n = int(min(8, max(3, -(-(1 << 29) // int(N * K * BYTES_PER_WEIGHT[fmt])))))
+            lins[fmt] = linears(fmt, N, K, n)
+        for M in (64, 512):
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+            xq = ops.quant_mx(x)
+            sp = ops.tile_gemm_splits_fp4(M, N, K)
+
+            def call(c, lin):
+                if c == "fp4_mfma":
+                    with ops.kernel_policy(fp4_mfma=True):
+                        return lin(x)
+                if c == "fp4_mfma_gemm":
+                    return ops.gemm_fp4_mx(xq, lin.weight_fp4, lin.weight_block_scale, sp)
+                return lin(x)
+
+            graphs = {c: graph([(lambda lin=lin, c=c: call(c, lin)) for lin in lins[wfmt[c]]])
+                      for c in cands}
+            samples = {c: [] for c in cands}
+            for _ in range(7):                       # interleaved: same box, same minute
+                for c in cands:
+                    samples[c].append(timed(graphs[c], 10) / len(lins[wfmt[c]]))
+            row = {}
+            for c in cands:
+                us = statistics.median(samples[c])
+                row[c] = {"us": round(us, 2), "TFLOPs": round(2.0 * M * N * K / us / 1e6, 1),
+                          "min_us": round(min(samples[c]), 2), "max_us": round(max(samples[c]), 2),
+                          "copies": len(lins[wfmt[c]])}
+            row["fp4_splits"] = sp
+            row["mfma_vs_dequant"] = round(row["fp4_mfma"]["us"] / row["fp4_dequant"]["us"], 3)
+            row["mfma_vs_fp8"] = round(row["fp4_mfma"]["us"] / row["fp8"]["us"], 3)
+            row["mfma_vs_bf16"] = round(row["fp4_mfma"]["us"] / row["bf16"]["us"], 3)
+            res["shapes"][f"{name}_M{M}"] = dict(N=N, K=K, M=M, **row)
+            print(f"{name:8s} M={M:3d} " + "  ".join(f"{c} {row[c]['us']:8.2f}" for c in cands)
+                  + f"  us; mfma/dequant {row['mfma_vs_dequant']:.3f} mfma/fp8 "
+                  f"{row['mfma_vs_fp8']:.3f} mfma/bf16 {row['mfma_vs_bf16']:.3f}", flush=True)
+            _save(a, "gemm.json", res)
+            del graphs
+            torch.cuda.empty_cache()
+        del lins
+        gc.collect()
+        torch.cuda.empty_cache()
+    return res
+
+
 # ----------------------------------------------------------------------------- engine decode
-def _decode_ms(a, quantize, batch, short, long_):
+def _decode_ms(a, quantize, batch, short, long_, kernels=""):
     """ms per decode step of ``batch`` sequences: two generate() calls that differ only in the
     number of decode steps (the prefill and the start-up cancel in the difference)."""
     torch = _torch()
-    from distributed_llm_inference.config import CacheConfig, ServeConfig, resolve_model
+    from distributed_llm_inference.config import CacheConfig, KernelPolicy, ServeConfig, resolve_model
     from distributed_llm_inference.runtime.engine import EngineConfig, LLMEngine
     from distributed_llm_inference.runtime.sequence import SamplingParams
     spec = resolve_model("llama-3-70b")
     if a.num_layers:
         spec = spec.replace(num_layers=a.num_layers, name=f"{spec.name}-{a.num_layers}L")
+    # always an explicit policy: the engine installs it process-wide, and the engines of one
+    # step run one after the other in this process
     cfg = EngineConfig(model=spec, random_init=True, seed=0, quantize=quantize,
+                       kernels=KernelPolicy().with_overrides(kernels),
                        cache=CacheConfig(block_size=64, gpu_memory_utilization=0.90),
                        serve=ServeConfig(max_batch_size=batch, max_num_batched_tokens=2048,
                                          max_seq_len=512, use_graphs=True,
@@ -179,6 +288,24 @@ def step_batch512(a):
         print(mode, res[mode], flush=True)
         _save(a, "decode_b512.json", res)
     res["mxfp4_vs_bf16"] = round(res["mxfp4"]["ms_per_step"] / res["bf16"]["ms_per_step"], 3)
+    # the MFMA-native fp4 tile GEMM (KernelPolicy.fp4_mfma) on and off in this same process,
+    # with fp8 and the bf16 run above for scale
+    mf = {"model": res["model"], "batch": 512, "num_layers": res["num_layers"], "unit": res["unit"],
+          "mxfp4_dequant": res["mxfp4"], "bf16": res["bf16"]}
+    for key, mode, kernels in (("mxfp4_mfma", "mxfp4", "fp4_mfma=1"),
+                               ("mxfp4_dequant_again", "mxfp4", "fp4_mfma=0"), ("fp8", "fp8", "")):
+        print(f"batch 512, {key}: building the engine", flush=True)
+        mf[key] = _decode_ms(a, mode, 512, 4, 28, kernels)
+        print(key, mf[key], flush=True)
+        _save(a, "decode_b512_mfma.json", mf)
+    on = mf["mxfp4_mfma"]["ms_per_step"]
+    # against the faster of the two flag-off runs (before and after the flag-on engine)
+    off = min(mf["mxfp4_dequant"]["ms_per_step"], mf["mxfp4_dequant_again"]["ms_per_step"])
+    mf["mfma_vs_dequant"] = round(on / off, 3)
+    mf["mfma_vs_fp8"] = round(on / mf["fp8"]["ms_per_step"], 3)
+    mf["mfma_vs_bf16"] = round(on / mf["bf16"]["ms_per_step"], 3)
+    mf["mfma_faster_than_dequant"] = bool(on < off)
+    _save(a, "decode_b512_mfma.json", mf)
     return res
 
 
@@ -188,7 +315,8 @@ def _save(a, name, res):
         f.write("\n")
 
 
-STEPS = {"gemv": (step_gemv, "gemv.json"), "decode": (step_decode, "decode_b1.json"),
+STEPS = {"gemv": (step_gemv, "gemv.json"), "gemm": (step_gemm, "gemm.json"),
+         "decode": (step_decode, "decode_b1.json"),
          "batch512": (step_batch512, "decode_b512.json")}
 
 
