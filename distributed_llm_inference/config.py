@@ -450,10 +450,18 @@ class KernelPolicy:
     # the weight to bf16.  Experimental and off: it changes the numerics of those products (fp8
     # activation rounding; docs/kernels.md "MXFP4 weights")
     fp4_mfma: bool = False
+    # MXFP4 weights: products of 3 to this many rows on the weight-streaming MFMA kernel
+    # (csrc/kernels/gemm_fp4_small.hip: the weight read once at 17/32 byte and widened in
+    # registers, bf16 activations -- the dequantise path's numerics) instead of dequantising the
+    # weight to bf16; checked before fp4_mfma.  0 = off, else 3..32 (docs/kernels.md "MXFP4
+    # weights" has the measured crossover)
+    fp4_small_m: int = 0
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 
     def __post_init__(self):
+        if self.fp4_small_m != 0 and not 3 <= self.fp4_small_m <= 32:
+            raise ValueError(f"fp4_small_m={self.fp4_small_m}: 0 (off) or 3..32")
         if self.gemm4_decode_sched not in (4, 6, 8, 9):
             raise ValueError(f"gemm4_decode_sched={self.gemm4_decode_sched}: 4, 6, 8 or 9")
         sel = self.fp8_gemm4

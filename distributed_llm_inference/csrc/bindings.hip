@@ -914,6 +914,38 @@ void skinny_gemm_fp4(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Ten
            "skinny_gemm_fp4");
 }
 
+// MXFP4 weights, 3-32 bf16 rows: the weight-streaming MFMA GEMM (gemm_fp4_small.hip)
+void small_gemm_fp4(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Tensor> bias,
+                    bool swiglu) {
+  CHECK_IN(out); CHECK_IN(x);
+  CHECK_BF16(out); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "small_gemm_fp4: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 3 && M <= 32, "small_gemm_fp4: M in [3, 32]");
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "small_gemm_fp4: needs K % 128 == 0");
+  check_mxfp4(w, bscale, K, "small_gemm_fp4");
+  const int64_t N = w.size(0);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= (1 << 24), "small_gemm_fp4: needs N % 16 == 0");
+  TORCH_CHECK(!swiglu || (N % 32 == 0 && !bias.has_value()),
+              "small_gemm_fp4: swiglu needs N % 32 == 0 and no bias");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == (swiglu ? N / 2 : N),
+              "small_gemm_fp4: shape mismatch");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
+                  bscale.device() == x.device(), "small_gemm_fp4: one device");
+  const dli::bf16* b = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N && bias->device() == x.device(),
+                "small_gemm_fp4: bias must have N entries");
+    b = bp(*bias);
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_small_gemm_fp4(bp(out), bp(x), w.data_ptr<uint8_t>(),
+                                      bscale.data_ptr<uint8_t>(), b, (int)M, (int)N, (int)K,
+                                      swiglu, cur_stream()),
+           "small_gemm_fp4");
+}
+
 // out (bf16, contiguous, N * K elements) = the dequantised MXFP4 weight [N, K]
 void dequant_mxfp4(Tensor out, Tensor w, Tensor bscale) {
   CHECK_IN(out); CHECK_BF16(out);
@@ -1145,6 +1177,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false, py::arg("norm_w") = py::none(),
         py::arg("res_in") = py::none(), py::arg("res_out") = py::none(), py::arg("eps") = 1e-5);
+  m.def("small_gemm_fp4", &small_gemm_fp4,
+        "y = x . dequant(W4)^T (+ bias), MXFP4 weights, 3-32 bf16 rows (weight-streaming MFMA GEMM)",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
+        py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
         py::arg("out"), py::arg("w"), py::arg("block_scale"));
   m.def("quant_mx", &quant_mx, "MX fp8 quantiser: bf16 [M, K] -> e4m3 bytes + e8m0 per (row, 128)",

@@ -188,6 +188,17 @@ class Linear(nn.Module):
         max_m = ops.policy().tile_gemm_max_m
         return max_m == 0 or rows <= max_m
 
+    def fp4_small_ok(self, x: Optional[torch.Tensor]) -> bool:
+        """Whether the product of ``x`` with these MXFP4 weights runs on the weight-streaming
+        MFMA kernel for 3 to ``KernelPolicy.fp4_small_m`` bf16 rows (ops.small_gemm_fp4).  Like
+        :meth:`fp4_mfma_ok`, shapes, dtype and policy only, never the device."""
+        max_m = ops.policy().fp4_small_m
+        if (self.weight_fp4 is None or not max_m or x is None or x.dim() != 2
+                or x.dtype != torch.bfloat16 or self.in_features % 128
+                or self.out_features % 16):
+            return False
+        return 3 <= x.shape[0] <= min(max_m, ops.FP4_SMALL_MAX_M)
+
     def gemv_ok(self, rows: int, swiglu: bool = False, bf16_rows: bool = True) -> bool:
         """Whether :meth:`gemv` takes a product of ``rows`` GPU rows (bf16 rows, or with
         ``bf16_rows=False`` the fused quantiser's fp8 rows for fp8 weights)."""
@@ -287,6 +298,10 @@ class Linear(nn.Module):
                 return y
             y = y.reshape(*x.shape[:-1], self.out_features)
             return y + self.bias if self.bias is not None else y
+        if self.fp4_small_ok(x):
+            # MXFP4 weights, 3 to fp4_small_m rows: the weight streamed once and widened in
+            # registers (csrc/kernels/gemm_fp4_small.hip); a plain bf16 tensor, nothing deferred
+            return ops.small_gemm_fp4(x, self.weight_fp4, self.weight_block_scale, self.bias)
         if self.fp4_mfma_ok(x):
             # MXFP4 weights, more than 2 rows: rows quantised to MX fp8, then the fp4 x fp8
             # block-scaled MFMA tile GEMM (csrc/kernels/gemm_fp4.hip) -- no dequantised weight

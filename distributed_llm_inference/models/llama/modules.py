@@ -218,6 +218,11 @@ class LlamaMLP(nn.Module):
             else:
                 h = ops.swiglu_interleaved(gp(None, (xq, xs)))
             return self.down_proj(h, defer_reduce=defer_reduce)
+        if self.fused_swiglu and gp.bias is None and gp.fp4_small_ok(normed):
+            # MXFP4, 3 to KernelPolicy.fp4_small_m rows: the weight-streaming MFMA kernel with
+            # SwiGLU in its epilogue; down_proj dispatches itself
+            h = ops.small_gemm_fp4(normed, gp.weight_fp4, gp.weight_block_scale, swiglu=True)
+            return self.down_proj(h, defer_reduce=defer_reduce)
         if self.fused_swiglu and gp.fp4_mfma_ok(normed):
             # MXFP4 on the fp4 x fp8 MFMA tile GEMM (KernelPolicy.fp4_mfma), SwiGLU in its epilogue
             if gp.in_features // 128 <= ops.FP4_MAX_KTILES:

@@ -1220,6 +1220,30 @@ def skinny_gemm_fp4(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
     return out
 
 
+FP4_SMALL_MAX_M = 32    # kernel limit of small_gemm_fp4: two 16-column MFMA tiles of rows
+
+
+def small_gemm_fp4(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
+                   bias: Optional[torch.Tensor] = None, swiglu: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = x . dequant(packed, scales)^T (+ bias)`` for 3-32 bf16 rows with MXFP4 weights: the
+    weight streamed once at 17/32 byte per weight, widened to bf16 in registers and multiplied on
+    the bf16 MFMA (gemm_fp4_small.hip) -- the dequantise path's product up to summation order, no
+    activation rounding.  K % 128 == 0, N % 16 == 0.  ``swiglu``: the weight is a
+    swiglu_interleave'd gate|up weight (N % 32 == 0, no bias), returns silu(gate) * up."""
+    M, N = x.shape[0], packed.shape[0]
+    if not _gpu(x):
+        y = x.float() @ ref.dequantize_mxfp4(packed, scales).float().t()
+        if bias is not None:
+            y = y + bias.float()
+        y = _swiglu_ref(y) if swiglu else y.to(torch.bfloat16)
+        return out.copy_(y) if out is not None else y
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=x.device)
+    native().small_gemm_fp4(out, x.contiguous(), packed, scales, bias, swiglu)
+    return out
+
+
 def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor],
                          bias: Optional[torch.Tensor], positions: Optional[torch.Tensor],
                          slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],
