@@ -456,12 +456,20 @@ class KernelPolicy:
     # weight to bf16; checked before fp4_mfma.  0 = off, else 3..32 (docs/kernels.md "MXFP4
     # weights" has the measured crossover)
     fp4_small_m: int = 0
+    # fp8 weights: products of 3 to this many bf16 rows on the weight-streaming MFMA kernel
+    # (csrc/kernels/gemm_fp8_small.hip: the weight read once and widened to bf16 in registers, the
+    # activations never quantised -- the fp8 GEMV's numerics for bf16 rows) instead of quantising
+    # the rows for torch._scaled_mm or the block-scaled tile GEMM.  0 = off, else 3..32
+    # (docs/kernels.md "fp8 weights, 3-32 rows" has the measured crossover)
+    fp8_small_m: int = 0
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 
     def __post_init__(self):
         if self.fp4_small_m != 0 and not 3 <= self.fp4_small_m <= 32:
             raise ValueError(f"fp4_small_m={self.fp4_small_m}: 0 (off) or 3..32")
+        if self.fp8_small_m != 0 and not 3 <= self.fp8_small_m <= 32:
+            raise ValueError(f"fp8_small_m={self.fp8_small_m}: 0 (off) or 3..32")
         if self.gemm4_decode_sched not in (4, 6, 8, 9):
             raise ValueError(f"gemm4_decode_sched={self.gemm4_decode_sched}: 4, 6, 8 or 9")
         sel = self.fp8_gemm4

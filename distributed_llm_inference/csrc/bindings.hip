@@ -946,6 +946,39 @@ void small_gemm_fp4(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Tens
            "small_gemm_fp4");
 }
 
+// fp8 e4m3 weights [N, K] + fp32 per-row scales [N], 3-32 bf16 rows: the weight-streaming MFMA
+// GEMM (gemm_fp8_small.hip)
+void small_gemm_fp8(Tensor out, Tensor x, Tensor w, Tensor wscale, optional<Tensor> bias,
+                    bool swiglu) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w); CHECK_IN(wscale);
+  CHECK_BF16(out); CHECK_BF16(x); CHECK_F32(wscale);
+  TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, "small_gemm_fp8: fp8 e4m3fn weights");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && w.dim() == 2, "small_gemm_fp8: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M >= 3 && M <= 32, "small_gemm_fp8: M in [3, 32]");
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "small_gemm_fp8: needs K % 128 == 0");
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= (1 << 24), "small_gemm_fp8: needs N % 16 == 0");
+  TORCH_CHECK(w.size(1) == K && wscale.numel() == N, "small_gemm_fp8: weight [N, K], N scales");
+  TORCH_CHECK(!swiglu || (N % 32 == 0 && !bias.has_value()),
+              "small_gemm_fp8: swiglu needs N % 32 == 0 and no bias");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == (swiglu ? N / 2 : N),
+              "small_gemm_fp8: shape mismatch");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
+                  wscale.device() == x.device(), "small_gemm_fp8: one device");
+  const dli::bf16* b = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N && bias->device() == x.device(),
+                "small_gemm_fp8: bias must have N entries");
+    b = bp(*bias);
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_small_gemm_fp8(bp(out), bp(x), static_cast<const uint8_t*>(w.data_ptr()),
+                                      wscale.data_ptr<float>(), b, (int)M, (int)N, (int)K,
+                                      swiglu, cur_stream()),
+           "small_gemm_fp8");
+}
+
 // out (bf16, contiguous, N * K elements) = the dequantised MXFP4 weight [N, K]
 void dequant_mxfp4(Tensor out, Tensor w, Tensor bscale) {
   CHECK_IN(out); CHECK_BF16(out);
@@ -1180,6 +1213,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("small_gemm_fp4", &small_gemm_fp4,
         "y = x . dequant(W4)^T (+ bias), MXFP4 weights, 3-32 bf16 rows (weight-streaming MFMA GEMM)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
+        py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("small_gemm_fp8", &small_gemm_fp8,
+        "y = (x . W8^T) * w_scale (+ bias), fp8 weights, 3-32 bf16 rows (weight-streaming MFMA GEMM)",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("w_scale"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
         py::arg("out"), py::arg("w"), py::arg("block_scale"));

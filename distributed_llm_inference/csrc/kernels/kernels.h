@@ -155,6 +155,13 @@ int launch_dequant_mxfp4(bf16* out, const uint8_t* W, const uint8_t* bscale, siz
 int launch_small_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8_t* bscale,
                           const bf16* bias, int M, int N, int K, bool swiglu,
                           hipStream_t stream);
+// fp8 e4m3 weights x 3-32 bf16 rows, weight-streaming on the bf16 MFMA (gemm_fp8_small.hip):
+// y[M, N] = (x . W^T) * wscale[n] (+ bias), the weight widened in registers, the activations never
+// quantised; 3 <= M <= 32, N % 16 == 0, K % 128 == 0.  swiglu: W is swiglu_interleave'd gate|up
+// (N % 32 == 0, no bias), y is silu(gate) * up [M, N / 2]
+int launch_small_gemm_fp8(bf16* y, const bf16* x, const uint8_t* W, const float* wscale,
+                          const bf16* bias, int M, int N, int K, bool swiglu,
+                          hipStream_t stream);
 // MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip):
 // C[M, N] = (e4m3(a_q) * 2^(a_mx - 127)) . (e2m1(W) * 2^(bscale - 127))^T, fp32 accumulation.
 // a_q [M, K] bytes, a_mx in mx_off layout (launch_quant_mx), W / bscale as above; N % 256 == 0,

@@ -199,6 +199,23 @@ class Linear(nn.Module):
             return False
         return 3 <= x.shape[0] <= min(max_m, ops.FP4_SMALL_MAX_M)
 
+    def fp8_small_ok(self, x: Optional[torch.Tensor]) -> bool:
+        """Whether the product of ``x`` with these fp8 weights runs on the weight-streaming MFMA
+        kernel for 3 to ``KernelPolicy.fp8_small_m`` bf16 rows (ops.small_gemm_fp8).  Like
+        :meth:`fp4_small_ok`, shapes, dtype and policy only, never the device."""
+        if x is None or x.dim() != 2 or x.dtype != torch.bfloat16:
+            return False
+        return self.fp8_small_rows(x.shape[0])
+
+    def fp8_small_rows(self, rows: int) -> bool:
+        """:meth:`fp8_small_ok` for ``rows`` 2-D bf16 rows that do not exist yet (a layer asking
+        for the projections further down)."""
+        max_m = ops.policy().fp8_small_m
+        if (self.weight_fp8 is None or not max_m or self.in_features % 128
+                or self.out_features % 16):
+            return False
+        return 3 <= rows <= min(max_m, ops.FP8_SMALL_MAX_M)
+
     def gemv_ok(self, rows: int, swiglu: bool = False, bf16_rows: bool = True) -> bool:
         """Whether :meth:`gemv` takes a product of ``rows`` GPU rows (bf16 rows, or with
         ``bf16_rows=False`` the fused quantiser's fp8 rows for fp8 weights)."""
@@ -337,6 +354,11 @@ class Linear(nn.Module):
             if self.bias is not None:
                 y = y + self.bias
             return y
+        if x_q is None and self.fp8_small_ok(x):
+            # fp8 weights, 3 to fp8_small_m bf16 rows: the weight streamed once and widened in
+            # registers (csrc/kernels/gemm_fp8_small.hip), no row quantisation; a plain bf16
+            # tensor, nothing deferred
+            return ops.small_gemm_fp8(x, self.weight_fp8, self.weight_scale, self.bias)
         if (x_q is None and x is not None and x.is_cuda and x.dim() == 2
                 and 1 <= x.shape[0] <= ops.SKINNY_DISPATCH_M and x.dtype == torch.bfloat16
                 and self.in_features % 16 == 0 and ops.policy().gemv):

@@ -108,7 +108,8 @@ class LlamaAttention(nn.Module):
         elif meta.is_decode:
             op = self.o_proj
             mx = (op.is_fp8 and op.bias is None and ops.policy().fp8_mx
-                  and ops.attn_decode_mx_ok(self.head_dim, meta.num_splits))
+                  and ops.attn_decode_mx_ok(self.head_dim, meta.num_splits)
+                  and not op.fp8_small_rows(T))   # those rows stay bf16 for ops.small_gemm_fp8
             if mx and q.is_cuda:
                 sp = ops.tile_gemm_splits_fp8(T, op.out_features, op.in_features)
                 mx = bool(sp) and ops.mx_tileable(op.in_features, sp)
@@ -196,6 +197,12 @@ class LlamaMLP(nn.Module):
             h = ops.llm_int8_linear(normed, gp.weight_int8, gp.weight_scale, gp.int8_threshold,
                                     wq_t=gp.weight_int8_t, swiglu=True)
             return self.down_proj(h, defer_reduce=defer_reduce)
+        if (self.fused_swiglu and gp.bias is None and x_q is None
+                and gp.fp8_small_ok(normed)):
+            # fp8, 3 to KernelPolicy.fp8_small_m bf16 rows: the weight-streaming MFMA kernel with
+            # SwiGLU in its epilogue, no row quantisation; down_proj dispatches itself
+            h = ops.small_gemm_fp8(normed, gp.weight_fp8, gp.weight_scale, swiglu=True)
+            return self.down_proj(h, defer_reduce=defer_reduce)
         if self.fused_swiglu and gp.is_fp8:
             xq, xs = x_q if x_q is not None else ops.quant_rowwise(normed)
             if xq.is_cuda and ops.tile_gemm_splits_fp8(xq.shape[0], gp.out_features,
@@ -238,6 +245,9 @@ class LlamaMLP(nn.Module):
                 h = ops.swiglu_interleaved(gp(normed))
             return self.down_proj(h, defer_reduce=defer_reduce)
         gu = gp(normed, x_q)
+        if x_q is None and self.down_proj.fp8_small_rows(gu.shape[0]) and gu.dim() == 2:
+            # fp8 down projection on ops.small_gemm_fp8 (KernelPolicy.fp8_small_m): bf16 h
+            return self.down_proj(ops.silu_mul(gu), defer_reduce=defer_reduce)
         if self.down_proj.is_fp8:  # SwiGLU fused with the fp8 quantisation of down_proj's input
             if not gu.is_cuda and ops.policy().fp8_mx and self.down_proj.bias is None:
                 # CPU reference of the GPU tile path: h handed over in MX form (per-(row,
@@ -268,7 +278,7 @@ class LlamaDecoderLayer(nn.Module):
         into the post-attention RMSNorm."""
         if self._gemv_norms(hidden):
             return self._forward_gemv(hidden, residual, meta, k_cache, v_cache, cos_sin, defer_out)
-        if self.self_attn.qkv_proj.is_fp8:
+        if self.self_attn.qkv_proj.is_fp8 and not self._fp8_small(hidden):
             return self._forward_fp8(hidden, residual, meta, k_cache, v_cache, cos_sin, defer_out)
         first = residual is None
         if first:
@@ -295,6 +305,18 @@ class LlamaDecoderLayer(nn.Module):
         return (M * self.hidden_size * 2 <= 65536 and m.fused_swiglu
                 and a.qkv_proj.gemv_ok(M) and a.o_proj.gemv_ok(M)
                 and m.gate_up_proj.gemv_ok(M, swiglu=True) and m.down_proj.gemv_ok(M))
+
+    def _fp8_small(self, hidden) -> bool:
+        """3 to KernelPolicy.fp8_small_m bf16 rows whose four fp8 projections all run on the
+        weight-streaming MFMA kernel (Linear.fp8_small_ok): the layer then takes the generic body
+        (bf16 RMSNorms, no row quantiser) instead of ``_forward_fp8``.  Shapes, dtype and policy
+        only, so the CPU takes the same branch."""
+        if (not ops.policy().fp8_small_m or not isinstance(hidden, torch.Tensor)
+                or hidden.dim() != 2 or hidden.dtype != torch.bfloat16):
+            return False
+        a, m, M = self.self_attn, self.mlp, hidden.shape[0]
+        return (a.qkv_proj.fp8_small_rows(M) and a.o_proj.fp8_small_rows(M)
+                and m.gate_up_proj.fp8_small_rows(M) and m.down_proj.fp8_small_rows(M))
 
     def _forward_gemv(self, hidden, residual, meta, k_cache, v_cache, cos_sin, defer_out=False):
         """1-2 decode rows: input RMSNorm fused into the QKV GEMV, post-attention RMSNorm into the

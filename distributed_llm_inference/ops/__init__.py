@@ -1244,6 +1244,31 @@ def small_gemm_fp4(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
     return out
 
 
+FP8_SMALL_MAX_M = 32    # kernel limit of small_gemm_fp8: two 16-column MFMA tiles of rows
+
+
+def small_gemm_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor,
+                   bias: Optional[torch.Tensor] = None, swiglu: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = (x . w8^T) * w_scale (+ bias)`` for 3-32 bf16 rows with fp8 e4m3 weights [N, K] and one
+    fp32 scale per output row: the weight streamed once, widened to bf16 in registers and
+    multiplied on the bf16 MFMA (gemm_fp8_small.hip).  The activations are never quantised:
+    :func:`skinny_gemm_fp8`'s arithmetic for bf16 rows, on more of them.  K % 128 == 0,
+    N % 16 == 0.  ``swiglu``: the weight is a swiglu_interleave'd gate|up weight (N % 32 == 0, no
+    bias), returns silu(gate) * up."""
+    M, N = x.shape[0], w8.shape[0]
+    if not _gpu(x):
+        y = x.float() @ (w8.float() * w_scale.reshape(-1, 1)).t()
+        if bias is not None:
+            y = y + bias.float()
+        y = _swiglu_ref(y) if swiglu else y.to(torch.bfloat16)
+        return out.copy_(y) if out is not None else y
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=x.device)
+    native().small_gemm_fp8(out, x.contiguous(), w8, w_scale.reshape(-1), bias, swiglu)
+    return out
+
+
 def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor],
                          bias: Optional[torch.Tensor], positions: Optional[torch.Tensor],
                          slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],
