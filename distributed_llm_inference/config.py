@@ -18,6 +18,10 @@ import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+# head sizes the fused q/k RMSNorm takes (csrc/kernels/rope_cache.hip: a head's head_dim / 16
+# lanes must be a power of two)
+QK_NORM_HEAD_DIMS = (32, 64, 128, 256)
+
 
 @dataclass(frozen=True)
 class ModelSpec:
@@ -44,7 +48,7 @@ class ModelSpec:
     attention_bias: bool = False
     mlp_bias: bool = False
     name: str = "custom"
-    # Llama-family variants: "llama" | "mistral" | "qwen2" (the HF model_type)
+    # Llama-family variants: "llama" | "mistral" | "qwen2" | "qwen3" (the HF model_type)
     model_type: str = "llama"
     # bias on o_proj; None = same as attention_bias (Llama).  Qwen2 has q/k/v bias only.
     o_proj_bias: Optional[bool] = None
@@ -53,6 +57,9 @@ class ModelSpec:
     # HF config.output_hidden_states: what LlamaBlock.forward does when its argument is None
     # (reference models/llama/model.py:35-37)
     output_hidden_states: bool = False
+    # Qwen3: every q and k head is RMS-normalised over head_dim (learned weights q_norm / k_norm)
+    # between the projection and RoPE
+    qk_norm: bool = False
 
     @property
     def rope_type(self) -> Optional[str]:
@@ -88,7 +95,8 @@ class ModelSpec:
         h, i = self.hidden_size, self.intermediate_size
         if self.arch == "gpt2":
             return 4 * h * h + 4 * h + 2 * h * i + i + h + 4 * h
-        return h * self.qkv_size + self.q_size * h + 3 * h * i + 2 * h
+        qk = 2 * self.head_dim if self.qk_norm else 0
+        return h * self.qkv_size + self.q_size * h + 3 * h * i + 2 * h + qk
 
     def param_count(self) -> int:
         emb = self.vocab_size * self.hidden_size
@@ -143,15 +151,29 @@ class ModelSpec:
                 mlp_bias=True,
                 name=cfg.get("_name_or_path", "gpt2") or "gpt2",
             )
-        if mt not in ("llama", "mistral", "qwen2"):
-            raise ValueError(f"unsupported model_type {mt!r} (supported: llama, mistral, qwen2, gpt2)")
+        if mt not in ("llama", "mistral", "qwen2", "qwen3"):
+            raise ValueError(f"unsupported model_type {mt!r} (supported: llama, mistral, qwen2, "
+                             "qwen3, gpt2)")
         # Qwen2: q/k/v projections always carry a bias, o_proj never does (no config key)
         qwen2 = mt == "qwen2"
+        # Qwen3: per-head q/k RMSNorm; attention_bias from the config, for q/k/v and o_proj alike
+        qwen3 = mt == "qwen3"
         sw = cfg.get("sliding_window")
-        if qwen2 and not cfg.get("use_sliding_window", False):
+        if (qwen2 or qwen3) and not cfg.get("use_sliding_window", False):
             sw = None
         nh = cfg["num_attention_heads"]
         h = cfg["hidden_size"]
+        if qwen3:
+            mwl = cfg.get("max_window_layers")
+            if sw and mwl is not None and mwl < cfg["num_hidden_layers"]:
+                raise ValueError(
+                    f"qwen3: use_sliding_window with max_window_layers={mwl} < "
+                    f"{cfg['num_hidden_layers']} layers mixes windowed and full-attention layers; "
+                    "one window per model is supported")
+            hd = cfg.get("head_dim") or h // nh
+            if hd not in QK_NORM_HEAD_DIMS:
+                raise ValueError(f"qwen3: head_dim {hd} is not supported by the fused q/k norm "
+                                 f"(supported: {', '.join(map(str, QK_NORM_HEAD_DIMS))})")
         # transformers 4.x: rope_theta + rope_scaling; transformers 5.x: rope_parameters
         rp = cfg.get("rope_parameters") or {}
         rope_theta = cfg.get("rope_theta", rp.get("rope_theta", 10000.0))
@@ -188,6 +210,7 @@ class ModelSpec:
             o_proj_bias=False if qwen2 else None,
             sliding_window=int(sw) if sw else None,
             output_hidden_states=bool(cfg.get("output_hidden_states", False)),
+            qk_norm=qwen3,
         )
 
     def to_hf_dict(self) -> Dict[str, Any]:
@@ -201,13 +224,15 @@ class ModelSpec:
                 eos_token_id=self.eos_token_id,
             )
         arch_name = {"llama": "LlamaForCausalLM", "mistral": "MistralForCausalLM",
-                     "qwen2": "Qwen2ForCausalLM"}[self.model_type]
+                     "qwen2": "Qwen2ForCausalLM", "qwen3": "Qwen3ForCausalLM"}[self.model_type]
         extra: Dict[str, Any] = {}
         if self.model_type == "mistral":
             extra["sliding_window"] = self.sliding_window
-        if self.model_type == "qwen2":
+        if self.model_type in ("qwen2", "qwen3"):
             extra.update(use_sliding_window=self.sliding_window is not None,
                          sliding_window=self.sliding_window)
+        if self.model_type == "qwen3" and self.sliding_window is not None:
+            extra["max_window_layers"] = self.num_layers   # every layer windowed
         return dict(
             extra, model_type=self.model_type, architectures=[arch_name],
             vocab_size=self.vocab_size,
@@ -258,6 +283,24 @@ PRESETS: Dict[str, ModelSpec] = {
         intermediate_size=18944, num_layers=28, num_heads=28, num_kv_heads=4, head_dim=128,
         rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=32768,
         bos_token_id=151643, eos_token_id=151645, attention_bias=True, o_proj_bias=False),
+    # Qwen3 (per-head q/k RMSNorm, explicit head_dim, no attention bias).  These three were
+    # written down without access to the published config.json files: they serve as shapes; a
+    # real checkpoint's config.json is parsed (from_hf_config), never looked up here.
+    "qwen3-8b": ModelSpec(
+        name="qwen3-8b", model_type="qwen3", qk_norm=True, vocab_size=151936, hidden_size=4096,
+        intermediate_size=12288, num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128,
+        rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=40960,
+        bos_token_id=151643, eos_token_id=151645),
+    "qwen3-32b": ModelSpec(
+        name="qwen3-32b", model_type="qwen3", qk_norm=True, vocab_size=151936, hidden_size=5120,
+        intermediate_size=25600, num_layers=64, num_heads=64, num_kv_heads=8, head_dim=128,
+        rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=40960,
+        bos_token_id=151643, eos_token_id=151645),
+    "qwen3-0.6b": ModelSpec(
+        name="qwen3-0.6b", model_type="qwen3", qk_norm=True, vocab_size=151936, hidden_size=1024,
+        intermediate_size=3072, num_layers=28, num_heads=16, num_kv_heads=8, head_dim=128,
+        rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=40960,
+        tie_word_embeddings=True, bos_token_id=151643, eos_token_id=151645),
     # tiny configs for CPU tests / smoke
     "tiny-llama": ModelSpec(
         name="tiny-llama", vocab_size=512, hidden_size=128, intermediate_size=256, num_layers=4,

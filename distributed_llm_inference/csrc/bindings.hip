@@ -183,7 +183,8 @@ bool check_cache(const Tensor& k_cache, const Tensor& v_cache, int64_t nkv, int6
 void rope_cache(Tensor qkv, optional<Tensor> positions, optional<Tensor> slot_mapping,
                 optional<Tensor> cos_sin, Tensor q_out, optional<Tensor> q_sink_out,
                 int64_t window, Tensor k_cache, Tensor v_cache, int64_t nh, int64_t nkv,
-                double k_scale, double v_scale) {
+                double k_scale, double v_scale, optional<Tensor> q_norm,
+                optional<Tensor> k_norm, double norm_eps) {
   CHECK_DEV(qkv);
   // qkv: the bf16 GEMM output [T, *], or its un-reduced split-K partials [S, T, N] (fp32, or
   // bf16 from the fp8 path's gemm_tile epilogue 4)
@@ -248,8 +249,27 @@ void rope_cache(Tensor qkv, optional<Tensor> positions, optional<Tensor> slot_ma
   p.nkv = (int)nkv;
   p.D = (int)D;
   p.bs = (int)k_cache.size(2);
+  // Qwen3: per-head RMSNorm weights of q and k [D], applied before the rotation
+  TORCH_CHECK(q_norm.has_value() == k_norm.has_value(),
+              "rope_cache: q_norm and k_norm must be given together");
+  if (q_norm.has_value()) {
+    for (const Tensor* w : {&*q_norm, &*k_norm}) {
+      CHECK_IN(*w); CHECK_BF16(*w);
+      TORCH_CHECK(w->device() == qkv.device(), "rope_cache: norm weight on another device");
+      TORCH_CHECK(w->numel() == D, "rope_cache: q_norm / k_norm must have head_dim elements");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(w->data_ptr()) % 16 == 0,
+                  "rope_cache: q_norm / k_norm must be 16-byte aligned");
+    }
+    TORCH_CHECK(norm_eps >= 0, "rope_cache: norm_eps must not be negative");
+    p.q_norm_w = bp(*q_norm);
+    p.k_norm_w = bp(*k_norm);
+    p.qk_eps = (float)norm_eps;
+  }
   const c10::hip::HIPGuardMasqueradingAsCUDA g(qkv.device());
-  check_rc(dli::launch_rope_cache(p, (int)T, cur_stream()), "rope_cache");
+  const int rc = dli::launch_rope_cache(p, (int)T, cur_stream());
+  TORCH_CHECK(rc != -3, "rope_cache: q/k norm needs head_dim 32, 64, 128 or 256 and qkv row "
+              "strides that are multiples of 8 (head_dim ", D, ")");
+  check_rc(rc, "rope_cache");
 }
 
 // ------------------------------------------------------------------------------ attention
@@ -1157,7 +1177,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("interleaved") = false);
   m.def("gelu_bias", &gelu_bias, "gelu_tanh(x + bias)");
   m.def("add", &add, "out = a + b");
-  m.def("rope_cache", &rope_cache, "fused RoPE + paged KV cache write");
+  m.def("rope_cache", &rope_cache, "fused RoPE + paged KV cache write", py::arg("qkv"),
+        py::arg("positions"), py::arg("slot_mapping"), py::arg("cos_sin"), py::arg("q_out"),
+        py::arg("q_sink_out"), py::arg("window"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("nh"), py::arg("nkv"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(),
+        py::arg("norm_eps") = 1e-6);
   m.def("attn_decode", &attn_decode, "paged GQA decode attention (split-K)", py::arg("out"),
         py::arg("q"), py::arg("q_sink"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("scale"), py::arg("n_sink"),

@@ -58,6 +58,12 @@ struct RopeCacheParams {
   int parts_bf16;
   int splits;
   long split_stride;      // elements between consecutive partials (T * qkv_stride)
+  // optional (Qwen3): per-head RMSNorm of q and k over D before the rotation, y = x * rsqrt(
+  // mean(x^2) + qk_eps) * w rounded to bf16 once; both weights or neither (nullptr: no norm).
+  // 16-byte kernel only, D in {32, 64, 128, 256}
+  const bf16* q_norm_w;   // [D]
+  const bf16* k_norm_w;   // [D]
+  float qk_eps;
 };
 
 struct SampleParams {

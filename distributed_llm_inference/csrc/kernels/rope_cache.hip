@@ -199,7 +199,12 @@ __device__ __forceinline__ bf16x8 load_qkv8(const RopeCacheParams& p, const bf16
 #ifndef ROPE_THREADS
 #define ROPE_THREADS 64
 #endif
-template <bool FP8, int NS>
+// QKN (Qwen3): every q and k head is RMS-normalised over D with learned weights before the
+// rotation -- y = bf16(x * rsqrt(mean(x^2) + eps) * w), ops/reference.py::rms_norm's arithmetic on
+// the bf16 value loaded (or summed from the partials) -- and the rotations, the fp8 conversion and
+// the stores take y where they take x otherwise; v is untouched.  `if constexpr`: the QKN = false
+// instantiations, which every other model runs, contain none of it.
+template <bool FP8, int NS, bool QKN = false>
 __global__ void __launch_bounds__(ROPE_THREADS) rope_cache_kernel_v8(RopeCacheParams p) {
   const int t = blockIdx.x;
   const int h_lo = blockIdx.y * kHeadsPerWG;
@@ -228,8 +233,35 @@ __global__ void __launch_bounds__(ROPE_THREADS) rope_cache_kernel_v8(RopeCachePa
   for (int it = rot_lo + threadIdx.x; it < rot_hi; it += blockDim.x) {
     const int head = it / gpr;
     const int i = (it % gpr) * 8;
-    const bf16x8 a = load_qkv8<NS>(p, row, t, head * D + i);
-    const bf16x8 b = load_qkv8<NS>(p, row, t, head * D + half + i);
+    bf16x8 a = load_qkv8<NS>(p, row, t, head * D + i);
+    bf16x8 b = load_qkv8<NS>(p, row, t, head * D + half + i);
+    if constexpr (QKN) {
+      // this lane's 16 of the head's D squares; explicit fma so that every instantiation (bf16
+      // input, fp32 / bf16 partials) accumulates in the same order with the same roundings
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x = (float)a[j], y = (float)b[j];
+        ss = __builtin_fmaf(x, x, ss);
+        ss = __builtin_fmaf(y, y, ss);
+      }
+      // butterfly over the head's gpr = D/16 lanes.  The workgroup's items start at h_lo * gpr,
+      // so item `it` runs on lane (it - h_lo * gpr) % 64 and, gpr being a power of two <= 16
+      // (checked by the launcher), a head's lanes are gpr consecutive lanes aligned to gpr:
+      // lane ^ m stays inside the head for every m < gpr.  rot_hi is a multiple of gpr too, so
+      // a head's lanes are all inside this loop trip or all outside it, and the shuffle (which
+      // sits before the q / k branch) never reads an inactive lane.
+      for (int m = 1; m < gpr; m <<= 1) ss += __shfl_xor(ss, m);
+      const float r = rsqrtf(ss / (float)D + p.qk_eps);
+      const bf16* w = head < p.nh ? p.q_norm_w : p.k_norm_w;
+      const bf16x8 wa = *reinterpret_cast<const bf16x8*>(w + i);
+      const bf16x8 wb = *reinterpret_cast<const bf16x8*>(w + half + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        a[j] = (bf16)((float)a[j] * r * (float)wa[j]);
+        b[j] = (bf16)((float)b[j] * r * (float)wb[j]);
+      }
+    }
     bf16x8 oa = a, ob = b;
     if (cs) rotate8(a, b, cs, i, half, oa, ob);
     if (head < p.nh) {
@@ -299,7 +331,23 @@ int launch_rope_cache(const RopeCacheParams& p, int num_tokens, hipStream_t stre
   // partial (otherwise the 4-element kernel)
   const bool v8 = p.D % 16 == 0 && p.qkv_stride % 8 == 0 &&
                   (p.qkv_parts == nullptr || p.split_stride % 8 == 0);
-#define ROPE_LAUNCH(NS)                                                   \
+  if (p.q_norm_w != nullptr || p.k_norm_w != nullptr) {
+    // per-head q/k RMSNorm: the 16-byte kernel only, a head's D/16 lanes a power of two within
+    // one wave's 8 heads; anything else is an error, never the un-normalised kernel
+    if (p.q_norm_w == nullptr || p.k_norm_w == nullptr) return -3;
+    if (!v8 || !(p.D == 32 || p.D == 64 || p.D == 128 || p.D == 256)) return -3;
+#define ROPE_LAUNCH_QKN(NS)                                                             \
+  do {                                                                                  \
+    if (p.kv_fp8)                                                                       \
+      rope_cache_kernel_v8<true, NS, true><<<grid, ROPE_THREADS, 0, stream>>>(p);       \
+    else                                                                                \
+      rope_cache_kernel_v8<false, NS, true><<<grid, ROPE_THREADS, 0, stream>>>(p);      \
+  } while (0)
+    SPLITS_SWITCH(ns, ROPE_LAUNCH_QKN)
+#undef ROPE_LAUNCH_QKN
+    return 0;
+  }
+#define ROPE_LAUNCH(NS)                                                 \
   do {                                                                 \
     if (v8) {                                                          \
       if (p.kv_fp8)                                                    \

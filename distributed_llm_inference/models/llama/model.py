@@ -59,7 +59,7 @@ class LlamaBlock(nn.Module):
         holds the same weights as the unsplit model)."""
         for layer in self.layers:
             for name, p in layer.named_parameters():
-                if name.endswith("layernorm.weight"):
+                if name.endswith(("layernorm.weight", "q_norm.weight", "k_norm.weight")):
                     p.data.fill_(1.0)
                 elif name.endswith("bias"):
                     p.data.zero_()

@@ -72,6 +72,13 @@ class LlamaAttention(nn.Module):
         self.o_proj = Linear(spec.q_size, spec.hidden_size, bias=spec.has_o_proj_bias, dtype=dtype,
                              device=device)
         self.qkv_proj.role, self.o_proj.role = "qkv", "o"
+        # Qwen3: every q / k head RMS-normalised over head_dim before RoPE, inside the RoPE /
+        # KV-write kernel (csrc/kernels/rope_cache.hip); the weights stay bf16 under every
+        # weight-quantisation mode
+        self.qk_norm = spec.qk_norm
+        if spec.qk_norm:
+            self.q_norm = RMSNorm(spec.head_dim, spec.rms_norm_eps, device, dtype)
+            self.k_norm = RMSNorm(spec.head_dim, spec.rms_norm_eps, device, dtype)
 
     def forward(self, normed: Optional[torch.Tensor], meta: AttnMetadata, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, cos_sin: torch.Tensor, x_q=None, defer_reduce: bool = False,
@@ -80,10 +87,13 @@ class LlamaAttention(nn.Module):
         RMSNorm itself (1-2 decode rows, LlamaDecoderLayer._forward_gemv)."""
         q = None
         if norm is not None:
-            # 1-2 rows: RMSNorm -> QKV -> RoPE / KV write in one GEMV launch when it applies
-            q = self.qkv_proj.gemv_qkv_rope(normed, meta, k_cache, v_cache, cos_sin,
-                                            self.num_heads, self.num_kv_heads, self.head_dim,
-                                            norm=norm)
+            # 1-2 rows: RMSNorm -> QKV -> RoPE / KV write in one GEMV launch when it applies.
+            # Not with q/k norms: a wave of that epilogue holds two elements of a head, so the
+            # GEMV (input RMSNorm still fused) is followed by the RoPE kernel, one launch more
+            if not self.qk_norm:
+                q = self.qkv_proj.gemv_qkv_rope(normed, meta, k_cache, v_cache, cos_sin,
+                                                self.num_heads, self.num_kv_heads, self.head_dim,
+                                                norm=norm)
             q_sink = None
             if q is None:
                 qkv = self.qkv_proj.gemv(normed, norm=norm)
@@ -93,10 +103,12 @@ class LlamaAttention(nn.Module):
             # split-K partials of the QKV GEMM are summed inside the RoPE / KV-write kernel
             qkv = self.qkv_proj(normed, x_q, defer_reduce=True)
         if q is None:
+            qk = (dict(q_norm=self.q_norm.weight, k_norm=self.k_norm.weight,
+                       norm_eps=self.q_norm.eps) if self.qk_norm else {})
             q, q_sink = ops.rope_cache(qkv, meta.positions, meta.slot_mapping, cos_sin,
                                        self.num_heads, self.num_kv_heads, self.head_dim, k_cache,
                                        v_cache, window=meta.window, want_sink=meta.want_sink,
-                                       k_scale=meta.k_scale, v_scale=meta.v_scale)
+                                       k_scale=meta.k_scale, v_scale=meta.v_scale, **qk)
         T = q.shape[0]
         if meta.custom_mask is not None:
             # reference-API custom 4-D additive mask (reference model.py:115-119, modules.py:92-94):
@@ -372,6 +384,9 @@ class LlamaDecoderLayer(nn.Module):
                      g("self_attn.v_proj.bias")], 0).to(dt))
             if self.self_attn.o_proj.bias is not None:     # Llama attention_bias (not Qwen2)
                 self.self_attn.o_proj.bias.copy_(g("self_attn.o_proj.bias").to(dt))
+            if self.self_attn.qk_norm:                     # Qwen3 per-head q/k RMSNorm
+                self.self_attn.q_norm.weight.copy_(g("self_attn.q_norm.weight").to(dt))
+                self.self_attn.k_norm.weight.copy_(g("self_attn.k_norm.weight").to(dt))
             gu = torch.cat([g("mlp.gate_proj.weight"), g("mlp.up_proj.weight")], 0)
             if self.mlp.fused_swiglu:
                 gu = ops.swiglu_interleave(gu)
@@ -410,6 +425,9 @@ class LlamaDecoderLayer(nn.Module):
                        "self_attn.v_proj.bias": vb})
         if a.o_proj.bias is not None:
             sd["self_attn.o_proj.bias"] = a.o_proj.bias
+        if a.qk_norm:
+            sd.update({"self_attn.q_norm.weight": a.q_norm.weight,
+                       "self_attn.k_norm.weight": a.k_norm.weight})
         if m.gate_up_proj.bias is not None:
             gb, ub = m.gate_up_proj.bias.split([m.intermediate_size, m.intermediate_size], 0)
             sd.update({"mlp.gate_proj.bias": gb, "mlp.up_proj.bias": ub,

@@ -193,10 +193,15 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
                nkv: int, head_dim: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
                window: int = 0, want_sink: bool = False, q_out: Optional[torch.Tensor] = None,
                q_sink_out: Optional[torch.Tensor] = None, k_scale: float = 1.0,
-               v_scale: float = 1.0):
+               v_scale: float = 1.0, q_norm: Optional[torch.Tensor] = None,
+               k_norm: Optional[torch.Tensor] = None, norm_eps: float = 1e-6):
     """Rotate q/k, write k/v to the paged cache; returns ``(q [T, nh, D], q_sink or None)``.
     fp8 (e4m3fn) caches store ``k / k_scale`` and ``v / v_scale``.  ``qkv`` may be
-    :class:`SplitKPartials` (summed while loaded, bit-identical to the reduce pass)."""
+    :class:`SplitKPartials` (summed while loaded, bit-identical to the reduce pass).
+    ``q_norm`` / ``k_norm`` (Qwen3, both or neither): RMSNorm weights ``[head_dim]`` applied to
+    every q / k head before the rotation, inside the same kernel (head_dim 32 / 64 / 128 / 256)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_cache: q_norm and k_norm must be given together")
     if isinstance(qkv, SplitKPartials):
         T = qkv.shape[0]
         if q_out is None:
@@ -205,11 +210,13 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
             q_sink_out = torch.empty_like(q_out)
         native().rope_cache(qkv.parts, positions, slot_mapping, cos_sin, q_out,
                             q_sink_out if want_sink else None, int(window), k_cache, v_cache,
-                            int(nh), int(nkv), float(k_scale), float(v_scale))
+                            int(nh), int(nkv), float(k_scale), float(v_scale), q_norm, k_norm,
+                            float(norm_eps))
         return q_out, (q_sink_out if want_sink else None)
     if not _gpu(qkv):
         q, qs = ref.rope_cache(qkv, positions, slot_mapping, cos_sin, nh, nkv, head_dim, k_cache,
-                               v_cache, window, want_sink, k_scale, v_scale)
+                               v_cache, window, want_sink, k_scale, v_scale, q_norm, k_norm,
+                               norm_eps)
         if q_out is not None:
             q_out.copy_(q)
             q = q_out
@@ -224,7 +231,8 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
         q_sink_out = torch.empty_like(q_out)
     native().rope_cache(qkv, positions, slot_mapping, cos_sin, q_out,
                         q_sink_out if want_sink else None, int(window), k_cache, v_cache,
-                        int(nh), int(nkv), float(k_scale), float(v_scale))
+                        int(nh), int(nkv), float(k_scale), float(v_scale), q_norm, k_norm,
+                        float(norm_eps))
     return q_out, (q_sink_out if want_sink else None)
 
 

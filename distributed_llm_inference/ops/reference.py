@@ -67,11 +67,19 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
                slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],
                nh: int, nkv: int, D: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
                window: int = 0, want_sink: bool = False, k_scale: float = 1.0,
-               v_scale: float = 1.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               v_scale: float = 1.0, q_norm: Optional[torch.Tensor] = None,
+               k_norm: Optional[torch.Tensor] = None, norm_eps: float = 1e-6
+               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     T = qkv.shape[0]
     q = qkv[:, : nh * D].reshape(T, nh, D)
     k = qkv[:, nh * D: (nh + nkv) * D].reshape(T, nkv, D)
     v = qkv[:, (nh + nkv) * D: (nh + 2 * nkv) * D].reshape(T, nkv, D)
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_cache: q_norm and k_norm must be given together")
+    if q_norm is not None:
+        # Qwen3: every q / k head RMS-normalised over D (rounded to the input dtype) before RoPE
+        q, _ = rms_norm(q, q_norm, norm_eps)
+        k, _ = rms_norm(k, k_norm, norm_eps)
     q_sink = None
     if cos_sin is not None:
         maxp = cos_sin.shape[0]

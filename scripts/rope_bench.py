@@ -5,7 +5,11 @@ distinct block each).  Partials rotate over 8 sets (past the MALL); calls are re
 hipGraph.
 
     python scripts/rope_bench.py [--rows 512] [--kv-fp8] [--iters 20]
-Prints one JSON line (us per call, TB/s of its HBM bytes)."""
+Prints one JSON line (us per call, TB/s of its HBM bytes).
+
+    python scripts/rope_bench.py --qk-norm [--kv-fp8] [--rounds 15]
+times the kernel with and without the per-head q/k RMSNorm (Qwen3) on the same inputs, the two
+graphs replayed alternately in one process; prints the median us of each and their ratio."""
 import argparse
 import json
 import os
@@ -25,6 +29,9 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--sets", type=int, default=8)
     ap.add_argument("--no-kv", action="store_true", help="slot -1: no cache writes (diagnostic)")
+    ap.add_argument("--qk-norm", action="store_true",
+                    help="A/B: with vs without the per-head q/k RMSNorm, interleaved")
+    ap.add_argument("--rounds", type=int, default=15, help="--qk-norm: alternating rounds")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     T, S, NSET = a.rows, a.splits, a.sets
@@ -43,30 +50,56 @@ def main():
     cs = ops.reference.build_cos_sin(D, 4096, 500000.0, None, device=dev)
     qo = [torch.empty(T, nh, D, dtype=torch.bfloat16, device=dev) for _ in range(NSET)]
 
-    def run():
-        for i in range(NSET):
-            ops.rope_cache(ops.SplitKPartials(parts[i]), pos, slots, cs, nh, nkv, D, kc, vc,
-                           q_out=qo[i], k_scale=0.5, v_scale=0.5)
+    qw = (1 + 0.3 * torch.randn(D, device=dev, generator=g)).to(torch.bfloat16)
+    kw = (1 + 0.3 * torch.randn(D, device=dev, generator=g)).to(torch.bfloat16)
 
-    gr = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        run()
-    torch.cuda.current_stream().wait_stream(s)
-    with torch.cuda.graph(gr):
-        run()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
+    def capture(norm):
+        kwargs = dict(q_norm=qw, k_norm=kw, norm_eps=1e-6) if norm else {}
+
+        def run():
+            for i in range(NSET):
+                ops.rope_cache(ops.SplitKPartials(parts[i]), pos, slots, cs, nh, nkv, D, kc, vc,
+                               q_out=qo[i], k_scale=0.5, v_scale=0.5, **kwargs)
+
+        gr = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            run()
+        torch.cuda.current_stream().wait_stream(s)
+        with torch.cuda.graph(gr):
+            run()
         gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / a.iters / NSET
+        torch.cuda.synchronize()
+        return gr
+
+    def time_us(gr):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / a.iters / NSET
+
     kvb = 1 if a.kv_fp8 else 2
     nbytes = S * T * N * 2 + T * nh * D * 2 + 2 * T * nkv * D * kvb
+    if a.qk_norm:
+        graphs = {"base": capture(False), "qk_norm": capture(True)}
+        t = {k: [] for k in graphs}
+        for _ in range(a.rounds):
+            for k, gr in graphs.items():
+                t[k].append(time_us(gr))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(json.dumps({"kernel": "rope_cache", "rows": T, "splits": S, "kv_fp8": a.kv_fp8,
+                          "no_kv": a.no_kv, "rounds": a.rounds,
+                          "us_base": round(med["base"], 2), "us_qk_norm": round(med["qk_norm"], 2),
+                          "ratio": round(med["qk_norm"] / med["base"], 3),
+                          "us_base_min_max": [round(min(t["base"]), 2), round(max(t["base"]), 2)],
+                          "us_qk_norm_min_max": [round(min(t["qk_norm"]), 2),
+                                                 round(max(t["qk_norm"]), 2)]}), flush=True)
+        return
+    us = time_us(capture(False))
     print(json.dumps({"kernel": "rope_cache", "rows": T, "splits": S, "kv_fp8": a.kv_fp8, "no_kv": a.no_kv,
                       "us": round(us, 2), "TBps": round(nbytes / us / 1e6, 2)}), flush=True)
 
