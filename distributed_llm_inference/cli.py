@@ -65,15 +65,19 @@ def _common(ap: argparse.ArgumentParser) -> None:
 
 
 def engine_config(a):
-    from .config import CacheConfig, KernelPolicy, ServeConfig
+    from .config import (CacheConfig, KernelPolicy, ServeConfig, refuse_moe_quantization,
+                         resolve_model)
     from .runtime.engine import EngineConfig
     if getattr(a, "transport", None):
         os.environ["DLI_TRANSPORT"] = a.transport   # read by every rank's make_transport
+    quantize = ("fp8" if a.fp8 else "int8" if a.int8
+                else "mxfp4" if getattr(a, "fp4", False) else False)
+    # sparse-MoE models take bf16 weights only: fail here, before any rank is started
+    refuse_moe_quantization(resolve_model(a.checkpoint or a.model), quantize)
     return EngineConfig(
         kernels=KernelPolicy().with_overrides(getattr(a, "kernels", "")),
         model=a.model, checkpoint=a.checkpoint, random_init=a.checkpoint is None, seed=a.seed,
-        quantize=("fp8" if a.fp8 else "int8" if a.int8
-                  else "mxfp4" if getattr(a, "fp4", False) else False),
+        quantize=quantize,
         int8_threshold=a.int8_threshold, pp=a.gpus // max(1, a.dp), dp=a.dp,
         cache=CacheConfig(block_size=a.block_size, gpu_memory_utilization=a.gpu_mem,
                           window_length=a.window, num_sink_tokens=a.sinks, dtype=a.kv_dtype),

@@ -21,6 +21,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 # head sizes the fused q/k RMSNorm takes (csrc/kernels/rope_cache.hip: a head's head_dim / 16
 # lanes must be a power of two)
 QK_NORM_HEAD_DIMS = (32, 64, 128, 256)
+# sparse MoE limits (csrc/kernels/moe.hip: a wave ranks <= 256 router logits, <= 8 slots per token)
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOPK = 8
 
 
 @dataclass(frozen=True)
@@ -48,7 +51,8 @@ class ModelSpec:
     attention_bias: bool = False
     mlp_bias: bool = False
     name: str = "custom"
-    # Llama-family variants: "llama" | "mistral" | "qwen2" | "qwen3" (the HF model_type)
+    # Llama-family variants: "llama" | "mistral" | "qwen2" | "qwen3" | "qwen3_moe" | "mixtral"
+    # (the HF model_type)
     model_type: str = "llama"
     # bias on o_proj; None = same as attention_bias (Llama).  Qwen2 has q/k/v bias only.
     o_proj_bias: Optional[bool] = None
@@ -60,6 +64,31 @@ class ModelSpec:
     # Qwen3: every q and k head is RMS-normalised over head_dim (learned weights q_norm / k_norm)
     # between the projection and RoPE
     qk_norm: bool = False
+    # sparse mixture-of-experts MLP in every layer ("qwen3_moe", "mixtral"): num_experts routed
+    # experts of width moe_intermediate_size, num_experts_per_tok of them per token, the top-k
+    # router weights optionally renormalised by their sum.  num_experts == 0: dense MLP
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = False
+
+    def __post_init__(self):
+        if self.num_experts == 0:
+            return
+        e, k, h, i = (self.num_experts, self.num_experts_per_tok, self.hidden_size,
+                      self.moe_intermediate_size)
+        if self.arch != "llama" or e < 0:
+            raise ValueError("sparse MoE layers need the llama architecture and num_experts > 0")
+        if e > MOE_MAX_EXPERTS:
+            raise ValueError(f"num_experts={e}: at most {MOE_MAX_EXPERTS} experts are supported")
+        if not 1 <= k <= min(MOE_MAX_TOPK, e):
+            raise ValueError(f"num_experts_per_tok={k}: 1..{MOE_MAX_TOPK} (and <= num_experts) "
+                             "is supported")
+        if h % 128 or i <= 0 or i % 128:
+            raise ValueError(f"sparse MoE needs hidden_size ({h}) and the expert width ({i}) to "
+                             "be multiples of 128 (csrc/kernels/moe.hip)")
+        if self.mlp_bias:
+            raise ValueError("sparse MoE experts with mlp_bias are not supported")
 
     @property
     def rope_type(self) -> Optional[str]:
@@ -96,7 +125,10 @@ class ModelSpec:
         if self.arch == "gpt2":
             return 4 * h * h + 4 * h + 2 * h * i + i + h + 4 * h
         qk = 2 * self.head_dim if self.qk_norm else 0
-        return h * self.qkv_size + self.q_size * h + 3 * h * i + 2 * h + qk
+        mlp = 3 * h * i
+        if self.num_experts:   # the router + every expert's gate, up and down
+            mlp = h * self.num_experts + self.num_experts * 3 * h * self.moe_intermediate_size
+        return h * self.qkv_size + self.q_size * h + mlp + 2 * h + qk
 
     def param_count(self) -> int:
         emb = self.vocab_size * self.hidden_size
@@ -151,13 +183,39 @@ class ModelSpec:
                 mlp_bias=True,
                 name=cfg.get("_name_or_path", "gpt2") or "gpt2",
             )
-        if mt not in ("llama", "mistral", "qwen2", "qwen3"):
+        if mt not in ("llama", "mistral", "qwen2", "qwen3", "qwen3_moe", "mixtral"):
             raise ValueError(f"unsupported model_type {mt!r} (supported: llama, mistral, qwen2, "
-                             "qwen3, gpt2)")
+                             "qwen3, qwen3_moe, mixtral, gpt2)")
         # Qwen2: q/k/v projections always carry a bias, o_proj never does (no config key)
         qwen2 = mt == "qwen2"
         # Qwen3: per-head q/k RMSNorm; attention_bias from the config, for q/k/v and o_proj alike
-        qwen3 = mt == "qwen3"
+        # (Qwen3-MoE: the same attention)
+        qwen3 = mt in ("qwen3", "qwen3_moe")
+        moe: Dict[str, Any] = {}
+        if mt == "qwen3_moe" and cfg.get("num_experts") is None:
+            # transformers 5.x serialises Qwen3MoeConfig.num_experts under Mixtral's name
+            cfg = dict(cfg, num_experts=cfg.get("num_local_experts"))
+        need = {"qwen3_moe": ("num_experts", "num_experts_per_tok", "moe_intermediate_size"),
+                "mixtral": ("num_local_experts", "num_experts_per_tok", "intermediate_size")}
+        lacking = [k for k in need.get(mt, ()) if cfg.get(k) is None]
+        if lacking:
+            raise ValueError(f"{mt}: the config lacks {', '.join(lacking)}")
+        if mt == "qwen3_moe":
+            # every layer sparse: HF makes layer i sparse when i is not in mlp_only_layers and
+            # (i + 1) % decoder_sparse_step == 0
+            if cfg.get("decoder_sparse_step", 1) != 1 or cfg.get("mlp_only_layers"):
+                raise ValueError(
+                    "qwen3_moe: decoder_sparse_step != 1 or a non-empty mlp_only_layers mixes "
+                    "dense and sparse layers; only all-sparse stacks are supported")
+            moe = dict(num_experts=cfg["num_experts"],
+                       num_experts_per_tok=cfg["num_experts_per_tok"],
+                       moe_intermediate_size=cfg["moe_intermediate_size"],
+                       norm_topk_prob=bool(cfg.get("norm_topk_prob", False)))
+        elif mt == "mixtral":
+            # the expert width is intermediate_size; the top-k weights are always renormalised
+            moe = dict(num_experts=cfg["num_local_experts"],
+                       num_experts_per_tok=cfg["num_experts_per_tok"],
+                       moe_intermediate_size=cfg["intermediate_size"], norm_topk_prob=True)
         sw = cfg.get("sliding_window")
         if (qwen2 or qwen3) and not cfg.get("use_sliding_window", False):
             sw = None
@@ -167,12 +225,12 @@ class ModelSpec:
             mwl = cfg.get("max_window_layers")
             if sw and mwl is not None and mwl < cfg["num_hidden_layers"]:
                 raise ValueError(
-                    f"qwen3: use_sliding_window with max_window_layers={mwl} < "
+                    f"{mt}: use_sliding_window with max_window_layers={mwl} < "
                     f"{cfg['num_hidden_layers']} layers mixes windowed and full-attention layers; "
                     "one window per model is supported")
             hd = cfg.get("head_dim") or h // nh
             if hd not in QK_NORM_HEAD_DIMS:
-                raise ValueError(f"qwen3: head_dim {hd} is not supported by the fused q/k norm "
+                raise ValueError(f"{mt}: head_dim {hd} is not supported by the fused q/k norm "
                                  f"(supported: {', '.join(map(str, QK_NORM_HEAD_DIMS))})")
         # transformers 4.x: rope_theta + rope_scaling; transformers 5.x: rope_parameters
         rp = cfg.get("rope_parameters") or {}
@@ -211,6 +269,7 @@ class ModelSpec:
             sliding_window=int(sw) if sw else None,
             output_hidden_states=bool(cfg.get("output_hidden_states", False)),
             qk_norm=qwen3,
+            **moe,
         )
 
     def to_hf_dict(self) -> Dict[str, Any]:
@@ -224,14 +283,25 @@ class ModelSpec:
                 eos_token_id=self.eos_token_id,
             )
         arch_name = {"llama": "LlamaForCausalLM", "mistral": "MistralForCausalLM",
-                     "qwen2": "Qwen2ForCausalLM", "qwen3": "Qwen3ForCausalLM"}[self.model_type]
+                     "qwen2": "Qwen2ForCausalLM", "qwen3": "Qwen3ForCausalLM",
+                     "qwen3_moe": "Qwen3MoeForCausalLM",
+                     "mixtral": "MixtralForCausalLM"}[self.model_type]
         extra: Dict[str, Any] = {}
-        if self.model_type == "mistral":
+        if self.model_type in ("mistral", "mixtral"):
             extra["sliding_window"] = self.sliding_window
-        if self.model_type in ("qwen2", "qwen3"):
+        if self.model_type == "mixtral":
+            extra.update(num_local_experts=self.num_experts,
+                         num_experts_per_tok=self.num_experts_per_tok)
+        if self.model_type == "qwen3_moe":
+            extra.update(num_experts=self.num_experts,
+                         num_experts_per_tok=self.num_experts_per_tok,
+                         moe_intermediate_size=self.moe_intermediate_size,
+                         norm_topk_prob=self.norm_topk_prob, decoder_sparse_step=1,
+                         mlp_only_layers=[])
+        if self.model_type in ("qwen2", "qwen3", "qwen3_moe"):
             extra.update(use_sliding_window=self.sliding_window is not None,
                          sliding_window=self.sliding_window)
-        if self.model_type == "qwen3" and self.sliding_window is not None:
+        if self.model_type in ("qwen3", "qwen3_moe") and self.sliding_window is not None:
             extra["max_window_layers"] = self.num_layers   # every layer windowed
         return dict(
             extra, model_type=self.model_type, architectures=[arch_name],
@@ -301,6 +371,19 @@ PRESETS: Dict[str, ModelSpec] = {
         intermediate_size=3072, num_layers=28, num_heads=16, num_kv_heads=8, head_dim=128,
         rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=40960,
         tie_word_embeddings=True, bos_token_id=151643, eos_token_id=151645),
+    # sparse MoE (written down like the Qwen3 presets above: shapes, not looked-up configs)
+    "qwen3-30b-a3b": ModelSpec(
+        name="qwen3-30b-a3b", model_type="qwen3_moe", qk_norm=True, vocab_size=151936,
+        hidden_size=2048, intermediate_size=6144, num_layers=48, num_heads=32, num_kv_heads=4,
+        head_dim=128, rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=40960,
+        bos_token_id=151643, eos_token_id=151645, num_experts=128, num_experts_per_tok=8,
+        moe_intermediate_size=768, norm_topk_prob=True),
+    "mixtral-8x7b": ModelSpec(
+        name="mixtral-8x7b", model_type="mixtral", vocab_size=32000, hidden_size=4096,
+        intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128,
+        rms_norm_eps=1e-5, rope_theta=1000000.0, max_position_embeddings=32768, bos_token_id=1,
+        eos_token_id=2, num_experts=8, num_experts_per_tok=2, moe_intermediate_size=14336,
+        norm_topk_prob=True),
     # tiny configs for CPU tests / smoke
     "tiny-llama": ModelSpec(
         name="tiny-llama", vocab_size=512, hidden_size=128, intermediate_size=256, num_layers=4,
@@ -317,6 +400,16 @@ PRESETS: Dict[str, ModelSpec] = {
         rope_theta=0.0, tie_word_embeddings=True, bos_token_id=1, eos_token_id=2,
         hidden_act="gelu_new", attention_bias=True, mlp_bias=True),
 }
+
+
+def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
+    """Weight quantisation of a sparse-MoE model is an error, not a fallback: the grouped expert
+    GEMM (csrc/kernels/moe.hip) takes bf16 expert weights only."""
+    if spec.num_experts and mode not in (False, None, "none", "bf16"):
+        mode = "fp8" if mode is True else mode
+        raise ValueError(f"{mode} weights are not supported for sparse MoE layers "
+                         f"({spec.model_type}, {spec.name}): the grouped expert GEMM takes bf16 "
+                         "expert weights only")
 
 
 def resolve_model(model: Any) -> ModelSpec:

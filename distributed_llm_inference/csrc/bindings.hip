@@ -999,6 +999,111 @@ void small_gemm_fp8(Tensor out, Tensor x, Tensor w, Tensor wscale, optional<Tens
            "small_gemm_fp8");
 }
 
+// ------------------------------------------------------------------------------ sparse MoE (moe.hip)
+void moe_topk(Tensor ids, Tensor w, Tensor logits, bool renorm) {
+  CHECK_IN(ids); CHECK_IN(w); CHECK_IN(logits);
+  CHECK_I32(ids); CHECK_F32(w); CHECK_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2 && ids.dim() == 2 && w.dim() == 2, "moe_topk: 2-D tensors");
+  const int64_t T = logits.size(0), E = logits.size(1), k = ids.size(1);
+  TORCH_CHECK(T >= 1 && T <= (1 << 24), "moe_topk: 1 <= T <= 2^24");
+  TORCH_CHECK(E >= 1 && E <= 256 && k >= 1 && k <= 8 && k <= E, "moe_topk: E <= 256, k <= min(8, E)");
+  TORCH_CHECK(ids.size(0) == T && w.size(0) == T && w.size(1) == k, "moe_topk: ids / w [T, k]");
+  TORCH_CHECK(ids.device() == logits.device() && w.device() == logits.device(),
+              "moe_topk: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  check_rc(dli::launch_moe_topk(ids.data_ptr<int>(), w.data_ptr<float>(), bp(logits), (int)T,
+                                (int)E, (int)k, renorm, cur_stream()), "moe_topk");
+}
+
+// the grouping tables of P = T k pairs over E experts, each checked against its size
+struct MoeTables {
+  int64_t P, cap;
+};
+MoeTables check_moe_tables(const Tensor& sorted_pairs, const Tensor& tile_expert,
+                           const Tensor& tile_start, const Tensor& tile_rows,
+                           const Tensor& n_tiles, int64_t T, int64_t E, int64_t k,
+                           const at::Device& dev, const char* what) {
+  CHECK_IN(sorted_pairs); CHECK_IN(tile_expert); CHECK_IN(tile_start); CHECK_IN(tile_rows);
+  CHECK_IN(n_tiles);
+  CHECK_I32(sorted_pairs); CHECK_I32(tile_expert); CHECK_I32(tile_start); CHECK_I32(tile_rows);
+  CHECK_I32(n_tiles);
+  TORCH_CHECK(T >= 1 && T <= (1 << 24) && E >= 1 && E <= 256 && k >= 1 && k <= 8, what,
+              ": 1 <= T <= 2^24, E <= 256, k <= 8");
+  const int64_t P = T * k, cap = dli::moe_tile_capacity((int)T, (int)E, (int)k);
+  TORCH_CHECK(cap <= 65535, what, ": more than 65535 tiles (T * k too large for one launch)");
+  TORCH_CHECK(sorted_pairs.numel() == P && tile_expert.numel() == cap &&
+                  tile_start.numel() == cap && tile_rows.numel() == cap && n_tiles.numel() == 1,
+              what, ": sorted_pairs [T k], tile tables [min(E, T k) + T k / 32], n_tiles [1]");
+  TORCH_CHECK(sorted_pairs.device() == dev && tile_expert.device() == dev &&
+                  tile_start.device() == dev && tile_rows.device() == dev &&
+                  n_tiles.device() == dev, what, ": one device");
+  return {P, cap};
+}
+
+void moe_group(Tensor ids, Tensor expert_count, Tensor expert_offset, Tensor sorted_pairs,
+               Tensor tile_expert, Tensor tile_start, Tensor tile_rows, Tensor n_tiles) {
+  CHECK_IN(ids); CHECK_I32(ids);
+  CHECK_IN(expert_count); CHECK_I32(expert_count);
+  CHECK_IN(expert_offset); CHECK_I32(expert_offset);
+  TORCH_CHECK(ids.dim() == 2, "moe_group: ids [T, k]");
+  const int64_t T = ids.size(0), k = ids.size(1), E = expert_count.numel();
+  const MoeTables tb = check_moe_tables(sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles,
+                                        T, E, k, ids.device(), "moe_group");
+  TORCH_CHECK(expert_offset.numel() == E + 1 && expert_count.device() == ids.device() &&
+                  expert_offset.device() == ids.device(),
+              "moe_group: expert_count [E], expert_offset [E + 1] on the ids' device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(ids.device());
+  check_rc(dli::launch_moe_group(ids.data_ptr<int>(), expert_count.data_ptr<int>(),
+                                 expert_offset.data_ptr<int>(), sorted_pairs.data_ptr<int>(),
+                                 tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
+                                 tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(), (int)T,
+                                 (int)E, (int)k, (int)tb.cap, cur_stream()), "moe_group");
+}
+
+// epilogue 0: out h [>= P, I] = swiglu(x[token] . W[e]^T), x [T, K], W [E, 2 I, K];
+// epilogue 1: out y [>= P, N] (row = pair index) = x[start + r] . W[e]^T, x = h [>= P, K], W [E, N, K]
+void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor tile_expert,
+                      Tensor tile_start, Tensor tile_rows, Tensor n_tiles, int64_t T, int64_t k,
+                      int64_t epilogue) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
+  CHECK_BF16(out); CHECK_BF16(x); CHECK_BF16(w);
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
+              "moe_grouped_gemm: out / x 2-D, w [E, N, K]");
+  TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_grouped_gemm: epilogue 0 (gate|up) or 1 (down)");
+  const int64_t E = w.size(0), N = w.size(1), K = w.size(2);
+  const MoeTables tb = check_moe_tables(sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles,
+                                        T, E, k, x.device(), "moe_grouped_gemm");
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "moe_grouped_gemm: needs K % 128 == 0");
+  TORCH_CHECK(N >= 32 && N % 32 == 0 && N <= (1 << 24), "moe_grouped_gemm: needs N % 32 == 0");
+  TORCH_CHECK(x.size(1) == K && x.size(0) >= (epilogue == 0 ? T : tb.P),
+              "moe_grouped_gemm: x [T, K] (gate|up) or [>= T k, K] (down)");
+  TORCH_CHECK(out.size(0) >= tb.P && out.size(1) == (epilogue == 0 ? N / 2 : N),
+              "moe_grouped_gemm: out [>= T k, N / 2] (gate|up) or [>= T k, N] (down)");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device(),
+              "moe_grouped_gemm: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_moe_grouped_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
+                                        tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
+                                        tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(),
+                                        (int)tb.cap, (int)T, (int)E, (int)k, (int)N, (int)K,
+                                        (int)epilogue, cur_stream()), "moe_grouped_gemm");
+}
+
+void moe_combine(Tensor out, Tensor y, Tensor w) {
+  CHECK_IN(out); CHECK_IN(y); CHECK_IN(w);
+  CHECK_BF16(out); CHECK_BF16(y); CHECK_F32(w);
+  TORCH_CHECK(out.dim() == 2 && y.dim() == 2 && w.dim() == 2, "moe_combine: 2-D tensors");
+  const int64_t T = out.size(0), H = out.size(1), k = w.size(1);
+  TORCH_CHECK(T >= 1 && T <= (1 << 24) && k >= 1 && k <= 8 && H >= 8 && H % 8 == 0 &&
+                  H <= (1 << 24), "moe_combine: k <= 8, H % 8 == 0");
+  TORCH_CHECK(w.size(0) == T && y.size(0) >= T * k && y.size(1) == H,
+              "moe_combine: w [T, k], y [>= T k, H]");
+  TORCH_CHECK(y.device() == out.device() && w.device() == out.device(), "moe_combine: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(out.device());
+  check_rc(dli::launch_moe_combine(bp(out), bp(y), w.data_ptr<float>(), (int)T, (int)k, (int)H,
+                                   cur_stream()), "moe_combine");
+}
+
 // out (bf16, contiguous, N * K elements) = the dequantised MXFP4 weight [N, K]
 void dequant_mxfp4(Tensor out, Tensor w, Tensor bscale) {
   CHECK_IN(out); CHECK_BF16(out);
@@ -1243,6 +1348,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y = (x . W8^T) * w_scale (+ bias), fp8 weights, 3-32 bf16 rows (weight-streaming MFMA GEMM)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("w_scale"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("moe_topk", &moe_topk, "router logits [T, E] -> top-k expert ids + bf16-rounded weights",
+        py::arg("ids"), py::arg("w"), py::arg("logits"), py::arg("renorm"));
+  m.def("moe_group", &moe_group,
+        "top-k ids [T, k] -> per-expert counts / offsets, stably sorted pairs and <= 32-row tiles",
+        py::arg("ids"), py::arg("expert_count"), py::arg("expert_offset"),
+        py::arg("sorted_pairs"), py::arg("tile_expert"), py::arg("tile_start"),
+        py::arg("tile_rows"), py::arg("n_tiles"));
+  m.def("moe_grouped_gemm", &moe_grouped_gemm,
+        "grouped weight-streaming MFMA GEMM over the routed experts (0: gate|up + SwiGLU, 1: down)",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
+        py::arg("tile_expert"), py::arg("tile_start"), py::arg("tile_rows"), py::arg("n_tiles"),
+        py::arg("T"), py::arg("k"), py::arg("epilogue"));
+  m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
+        py::arg("out"), py::arg("y"), py::arg("w"));
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
         py::arg("out"), py::arg("w"), py::arg("block_scale"));
   m.def("quant_mx", &quant_mx, "MX fp8 quantiser: bf16 [M, K] -> e4m3 bytes + e8m0 per (row, 128)",

@@ -168,6 +168,29 @@ int launch_small_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8_
 int launch_small_gemm_fp8(bf16* y, const bf16* x, const uint8_t* W, const float* wscale,
                           const bf16* bias, int M, int N, int K, bool swiglu,
                           hipStream_t stream);
+// Sparse MoE MLP on bf16 expert weights (moe.hip).  P = T k (token, slot) pairs; E <= 256, k <= 8.
+// Every grid depends on (T, E, k, N) only and every count is read from device memory.
+// tile table capacity: min(E, P) + P / 32
+int moe_tile_capacity(int T, int E, int k);
+// logits [T, E] -> ids [T, k] (descending probability, ties to the lower index) and w [T, k]
+// (fp32 softmax probabilities, renorm: divided by their top-k sum; rounded to bf16)
+int launch_moe_topk(int* ids, float* w, const bf16* logits, int T, int E, int k, bool renorm,
+                    hipStream_t stream);
+// ids [P] -> expert_count [E], expert_offset [E + 1], sorted_pairs [P] (stable sort of the pair
+// index by expert), tiles of <= 32 rows (tile_expert / tile_start / tile_rows [cap]), n_tiles [1]
+int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int* sorted_pairs,
+                     int* tile_expert, int* tile_start, int* tile_rows, int* n_tiles, int T, int E,
+                     int k, int cap, hipStream_t stream);
+// W [E, N, K], N % 32 == 0, K % 128 == 0.  epilogue 0 (gate|up): x [T, K] gathered by
+// sorted_pairs / k, W rows swiglu_interleave'd, out h [P, N / 2]; 1 (down): x = h [P, K], out
+// y [P, N] with tile row r at row sorted_pairs[start + r]
+int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+                            const int* tile_expert, const int* tile_start, const int* tile_rows,
+                            const int* n_tiles, int cap, int T, int E, int k, int N, int K,
+                            int epilogue, hipStream_t stream);
+// out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
+int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
+                       hipStream_t stream);
 // MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip):
 // C[M, N] = (e4m3(a_q) * 2^(a_mx - 127)) . (e2m1(W) * 2^(bscale - 127))^T, fp32 accumulation.
 // a_q [M, K] bytes, a_mx in mx_off layout (launch_quant_mx), W / bscale as above; N % 256 == 0,

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...config import ModelSpec, resolve_model
+from ...config import ModelSpec, refuse_moe_quantization, resolve_model
 from ...ops.reference import build_cos_sin
 from ..common import AttnMetadata, param_seed, seeded_normal_
 from .cache import KVPool, PartialLlamaSinkCache
@@ -73,8 +73,12 @@ class LlamaBlock(nn.Module):
             layer.mlp.set_fused_swiglu(on)
         return self
 
+    def _refuse_moe(self, mode: str) -> None:
+        refuse_moe_quantization(self.config, mode)
+
     def quantize_int8(self, threshold: float = 6.0) -> "LlamaBlock":
         """LLM.int8 weights for every projection (reference convert_to_optimized_block)."""
+        self._refuse_moe("int8")
         self.set_fused_swiglu(False)
         for layer in self.layers:
             for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj,
@@ -83,6 +87,7 @@ class LlamaBlock(nn.Module):
         return self
 
     def quantize_fp8(self) -> "LlamaBlock":
+        self._refuse_moe("fp8")
         self.set_fused_swiglu(False)
         for layer in self.layers:
             for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj,
@@ -92,6 +97,7 @@ class LlamaBlock(nn.Module):
 
     def quantize_mxfp4(self) -> "LlamaBlock":
         """MXFP4 weights (4-bit e2m1, e8m0 scale per 32 input features) for every projection."""
+        self._refuse_moe("mxfp4")
         self.set_fused_swiglu(False)
         for layer in self.layers:
             for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj,

@@ -270,6 +270,89 @@ class LlamaMLP(nn.Module):
         return self.down_proj(ops.silu_mul(gu), defer_reduce=defer_reduce)
 
 
+class MoEMLP(nn.Module):
+    """Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral; HF ``Qwen3MoeSparseMoeBlock``): a bf16
+    router ``gate`` (H -> E), and per token the ``top_k`` most probable of E SwiGLU experts,
+    weighted by their (optionally renormalised) router probabilities.
+
+        logits = gate(x)                                   # Linear.forward, bf16
+        route  = ops.moe_route(logits, k, renorm)          # csrc/kernels/moe.hip
+        h      = swiglu(x[token] . w_gate_up[e]^T)         # grouped GEMM, rows sorted by expert
+        y      = h . w_down[e]^T                           # grouped GEMM, rows back in pair order
+        out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) # fp32, slot order, one rounding
+
+    ``w_gate_up [E, 2I, H]`` holds every expert's rows in ``ops.swiglu_interleave`` order, always
+    (``set_fused_swiglu`` is a no-op); ``w_down [E, H, I]``.  Expert weights are bf16 only.  The
+    block returns a plain bf16 tensor: nothing is deferred to the next RMSNorm."""
+
+    def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16):
+        super().__init__()
+        if spec.hidden_act != "silu":
+            raise ValueError(f"unsupported MoE activation {spec.hidden_act!r}")
+        E, I, H = spec.num_experts, spec.moe_intermediate_size, spec.hidden_size
+        self.num_experts, self.top_k = E, spec.num_experts_per_tok
+        self.intermediate_size = I
+        self.norm_topk_prob = spec.norm_topk_prob
+        # checkpoint key names: Mixtral's block_sparse_moe.experts.{e}.w1 / w3 / w2
+        self.mixtral_keys = spec.model_type == "mixtral"
+        self.gate = Linear(H, E, bias=False, dtype=dtype, device=device)
+        self.gate.role = "router"
+        self.w_gate_up = nn.Parameter(torch.empty(E, 2 * I, H, dtype=dtype, device=device),
+                                      requires_grad=False)
+        self.w_down = nn.Parameter(torch.empty(E, H, I, dtype=dtype, device=device),
+                                   requires_grad=False)
+        self.fused_swiglu = True   # the experts' gate|up rows are always interleaved
+
+    def set_fused_swiglu(self, on: bool) -> None:
+        """No-op: the grouped GEMM's only epilogue reads interleaved rows."""
+
+    def forward(self, normed: torch.Tensor, x_q=None, defer_reduce: bool = False, norm=None):
+        if x_q is not None or norm is not None:
+            raise RuntimeError("MoEMLP takes normalised bf16 rows (the layer's generic body)")
+        return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
+                           self.norm_topk_prob)
+
+    # ------------------------------------------------------------------ weights
+    def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
+        """From a layer state dict ``sd`` (``g`` = its checked getter): the hub's per-expert keys
+        (Qwen3-MoE ``mlp.experts.{e}.{gate,up,down}_proj.weight``, Mixtral
+        ``block_sparse_moe.experts.{e}.{w1,w3,w2}.weight`` with w1 = gate, w3 = up, w2 = down), or
+        the fused 3-D tensors ``experts.gate_up_proj [E, 2I, H]`` (gate half first) and
+        ``experts.down_proj [E, H, I]`` under either prefix."""
+        pre = next((p for p in ("mlp.", "block_sparse_moe.") if p + "gate.weight" in sd), None)
+        if pre is None:
+            g("block_sparse_moe.gate.weight" if self.mixtral_keys else "mlp.gate.weight")
+        self.gate.weight.copy_(g(pre + "gate.weight").to(dt))
+        if pre + "experts.gate_up_proj" in sd:
+            gu, down = g(pre + "experts.gate_up_proj"), g(pre + "experts.down_proj")
+            if gu.shape != self.w_gate_up.shape or down.shape != self.w_down.shape:
+                raise ValueError(f"fused expert tensors {tuple(gu.shape)} / {tuple(down.shape)} "
+                                 f"do not match {tuple(self.w_gate_up.shape)} / "
+                                 f"{tuple(self.w_down.shape)}")
+            for e in range(self.num_experts):
+                self.w_gate_up[e].copy_(ops.swiglu_interleave(gu[e]).to(dt))
+            self.w_down.copy_(down.to(dt))
+            return
+        names = ("w1", "w3", "w2") if pre + "experts.0.w1.weight" in sd else (
+            "gate_proj", "up_proj", "down_proj")
+        for e in range(self.num_experts):
+            gate, up, down = (g(f"{pre}experts.{e}.{n}.weight") for n in names)
+            self.w_gate_up[e].copy_(ops.swiglu_interleave(torch.cat([gate, up], 0)).to(dt))
+            self.w_down[e].copy_(down.to(dt))
+
+    def hf_dict(self) -> dict:
+        """The hub's per-expert layout (inverse of :meth:`load_hf`)."""
+        pre, names = (("block_sparse_moe.", ("w1", "w3", "w2")) if self.mixtral_keys else
+                      ("mlp.", ("gate_proj", "up_proj", "down_proj")))
+        sd = {pre + "gate.weight": self.gate.weight}
+        I = self.intermediate_size
+        for e in range(self.num_experts):
+            gate, up = ops.swiglu_deinterleave(self.w_gate_up[e]).split([I, I], 0)
+            for n, w in zip(names, (gate, up, self.w_down[e])):
+                sd[f"{pre}experts.{e}.{n}.weight"] = w
+        return sd
+
+
 class LlamaDecoderLayer(nn.Module):
     """One decoder layer; ``layer_idx`` is the GLOBAL layer index (as in the reference)."""
 
@@ -278,7 +361,9 @@ class LlamaDecoderLayer(nn.Module):
         self.layer_idx = layer_idx
         self.hidden_size = spec.hidden_size
         self.self_attn = LlamaAttention(spec, layer_idx, device, dtype)
-        self.mlp = LlamaMLP(spec, device, dtype)
+        # sparse MoE (Qwen3-MoE, Mixtral): the layer always takes the generic body below
+        self.is_moe = spec.num_experts > 0
+        self.mlp = MoEMLP(spec, device, dtype) if self.is_moe else LlamaMLP(spec, device, dtype)
         self.input_layernorm = RMSNorm(spec.hidden_size, spec.rms_norm_eps, device, dtype)
         self.post_attention_layernorm = RMSNorm(spec.hidden_size, spec.rms_norm_eps, device, dtype)
 
@@ -308,8 +393,8 @@ class LlamaDecoderLayer(nn.Module):
     def _gemv_norms(self, hidden) -> bool:
         """1-2 decode rows whose four projections all run on the weight-streaming GEMV: the two
         RMSNorms then run inside the QKV and gate|up GEMVs (``_forward_gemv``)."""
-        if (not isinstance(hidden, torch.Tensor) or not hidden.is_cuda or hidden.dim() != 2
-                or hidden.dtype != torch.bfloat16 or not hidden.is_contiguous()
+        if (self.is_moe or not isinstance(hidden, torch.Tensor) or not hidden.is_cuda
+                or hidden.dim() != 2 or hidden.dtype != torch.bfloat16 or not hidden.is_contiguous()
                 or not (ops.policy().gemv and ops.policy().gemv_norm)):
             return False
         M = hidden.shape[0]
@@ -323,7 +408,7 @@ class LlamaDecoderLayer(nn.Module):
         weight-streaming MFMA kernel (Linear.fp8_small_ok): the layer then takes the generic body
         (bf16 RMSNorms, no row quantiser) instead of ``_forward_fp8``.  Shapes, dtype and policy
         only, so the CPU takes the same branch."""
-        if (not ops.policy().fp8_small_m or not isinstance(hidden, torch.Tensor)
+        if (self.is_moe or not ops.policy().fp8_small_m or not isinstance(hidden, torch.Tensor)
                 or hidden.dim() != 2 or hidden.dtype != torch.bfloat16):
             return False
         a, m, M = self.self_attn, self.mlp, hidden.shape[0]
@@ -387,15 +472,18 @@ class LlamaDecoderLayer(nn.Module):
             if self.self_attn.qk_norm:                     # Qwen3 per-head q/k RMSNorm
                 self.self_attn.q_norm.weight.copy_(g("self_attn.q_norm.weight").to(dt))
                 self.self_attn.k_norm.weight.copy_(g("self_attn.k_norm.weight").to(dt))
-            gu = torch.cat([g("mlp.gate_proj.weight"), g("mlp.up_proj.weight")], 0)
-            if self.mlp.fused_swiglu:
-                gu = ops.swiglu_interleave(gu)
-            self.mlp.gate_up_proj.weight.copy_(gu.to(dt))
-            self.mlp.down_proj.weight.copy_(g("mlp.down_proj.weight").to(dt))
-            if self.mlp.gate_up_proj.bias is not None:     # Llama mlp_bias
-                self.mlp.gate_up_proj.bias.copy_(torch.cat(
-                    [g("mlp.gate_proj.bias"), g("mlp.up_proj.bias")], 0).to(dt))
-                self.mlp.down_proj.bias.copy_(g("mlp.down_proj.bias").to(dt))
+            if self.is_moe:
+                self.mlp.load_hf(g, sd, dt)
+            else:
+                gu = torch.cat([g("mlp.gate_proj.weight"), g("mlp.up_proj.weight")], 0)
+                if self.mlp.fused_swiglu:
+                    gu = ops.swiglu_interleave(gu)
+                self.mlp.gate_up_proj.weight.copy_(gu.to(dt))
+                self.mlp.down_proj.weight.copy_(g("mlp.down_proj.weight").to(dt))
+                if self.mlp.gate_up_proj.bias is not None:     # Llama mlp_bias
+                    self.mlp.gate_up_proj.bias.copy_(torch.cat(
+                        [g("mlp.gate_proj.bias"), g("mlp.up_proj.bias")], 0).to(dt))
+                    self.mlp.down_proj.bias.copy_(g("mlp.down_proj.bias").to(dt))
             self.input_layernorm.weight.copy_(g("input_layernorm.weight").to(dt))
             self.post_attention_layernorm.weight.copy_(g("post_attention_layernorm.weight").to(dt))
 
@@ -405,18 +493,21 @@ class LlamaDecoderLayer(nn.Module):
         q, k, v = a.qkv_proj.weight.split([a.num_heads * a.head_dim,
                                            a.num_kv_heads * a.head_dim,
                                            a.num_kv_heads * a.head_dim], 0)
-        gu = m.gate_up_proj.weight
-        if m.fused_swiglu:
-            gu = ops.swiglu_deinterleave(gu)
-        gate, up = gu.split([m.intermediate_size, m.intermediate_size], 0)
         sd = {
             "self_attn.q_proj.weight": q, "self_attn.k_proj.weight": k,
             "self_attn.v_proj.weight": v, "self_attn.o_proj.weight": a.o_proj.weight,
-            "mlp.gate_proj.weight": gate, "mlp.up_proj.weight": up,
-            "mlp.down_proj.weight": m.down_proj.weight,
             "input_layernorm.weight": self.input_layernorm.weight,
             "post_attention_layernorm.weight": self.post_attention_layernorm.weight,
         }
+        if self.is_moe:
+            sd.update(m.hf_dict())
+        else:
+            gu = m.gate_up_proj.weight
+            if m.fused_swiglu:
+                gu = ops.swiglu_deinterleave(gu)
+            gate, up = gu.split([m.intermediate_size, m.intermediate_size], 0)
+            sd.update({"mlp.gate_proj.weight": gate, "mlp.up_proj.weight": up,
+                       "mlp.down_proj.weight": m.down_proj.weight})
         if a.qkv_proj.bias is not None:
             qb, kb, vb = a.qkv_proj.bias.split([a.num_heads * a.head_dim,
                                                 a.num_kv_heads * a.head_dim,
@@ -428,7 +519,7 @@ class LlamaDecoderLayer(nn.Module):
         if a.qk_norm:
             sd.update({"self_attn.q_norm.weight": a.q_norm.weight,
                        "self_attn.k_norm.weight": a.k_norm.weight})
-        if m.gate_up_proj.bias is not None:
+        if not self.is_moe and m.gate_up_proj.bias is not None:
             gb, ub = m.gate_up_proj.bias.split([m.intermediate_size, m.intermediate_size], 0)
             sd.update({"mlp.gate_proj.bias": gb, "mlp.up_proj.bias": ub,
                        "mlp.down_proj.bias": m.down_proj.bias})

@@ -1333,3 +1333,88 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     native().skinny_gemm(out, x, w, bias, swiglu, **(norm.kwargs() if norm is not None else {}))
     return out
 
+
+
+# ----------------------------------------------------------------------------- sparse MoE
+MoERouting = ref.MoERouting
+MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
+MOE_MAX_TOPK = ref.MOE_MAX_TOPK
+moe_tile_capacity = ref.moe_tile_capacity
+
+
+def moe_topk(logits: torch.Tensor, k: int, renorm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Router top-k on ``logits [T, E]`` (bf16): ``(ids [T, k] int32, w [T, k] fp32)`` -- softmax
+    in fp32, the k largest in descending order (ties to the lower index), optionally divided by
+    their sum, rounded to bf16 (HF ``Qwen3MoeTopKRouter``)."""
+    T, E = logits.shape
+    if not 1 <= k <= min(MOE_MAX_TOPK, E) or E > MOE_MAX_EXPERTS:
+        raise ValueError(f"moe_topk: E={E} (<= {MOE_MAX_EXPERTS}), k={k} (<= {MOE_MAX_TOPK})")
+    if not _gpu(logits):
+        return ref.moe_topk(logits, k, renorm)
+    ids = torch.empty(T, k, dtype=torch.int32, device=logits.device)
+    w = torch.empty(T, k, dtype=torch.float32, device=logits.device)
+    native().moe_topk(ids, w, logits.contiguous(), bool(renorm))
+    return ids, w
+
+
+def moe_group(topk_ids: torch.Tensor, topk_w: torch.Tensor, E: int) -> MoERouting:
+    """The expert grouping of explicit ``topk_ids [T, k]`` (int32): see :class:`MoERouting`.
+    Deterministic: ``sorted_pairs`` is the stable sort of the pair indices by expert."""
+    T, k = topk_ids.shape
+    if not _gpu(topk_ids):
+        return MoERouting(topk_ids, topk_w, *ref.moe_group(topk_ids, E))
+    cap, P = moe_tile_capacity(T, E, k), T * k
+    buf = torch.empty(E + (E + 1) + P + 3 * cap + 1, dtype=torch.int32, device=topk_ids.device)
+    count, offset, pairs, te, ts, tr, nt = buf.split([E, E + 1, P, cap, cap, cap, 1])
+    native().moe_group(topk_ids.contiguous(), count, offset, pairs, te, ts, tr, nt)
+    return MoERouting(topk_ids, topk_w, count, offset, pairs, te, ts, tr, nt)
+
+
+def moe_route(logits: torch.Tensor, k: int, renorm: bool) -> MoERouting:
+    """Top-k routing of ``logits [T, E]`` and its grouping by expert, without a host sync (every
+    count stays in device memory; grids depend on (T, E, k) only)."""
+    ids, w = moe_topk(logits, k, renorm)
+    return moe_group(ids, w, logits.shape[1])
+
+
+def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
+    ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
+    rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
+    ``sorted_pairs[j] // k``.  ``down=True``: ``x = h [P, I]``, ``w [E, H, I]``; returns
+    ``y [P, H]`` with row j of h at row ``sorted_pairs[j]`` (the pair index).  ``out`` may have
+    more than P rows; the rest are not touched."""
+    T, k = r.topk_ids.shape
+    P, N = T * k, w.shape[1]
+    if out is None:
+        out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=x.device)
+    if not _gpu(x):
+        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out)
+    native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
+                              r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0)
+    return out
+
+
+def moe_combine(y: torch.Tensor, topk_w: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t * k + slot])``, fp32, in slot order."""
+    T = topk_w.shape[0]
+    if not _gpu(y):
+        o = ref.moe_combine(y, topk_w)
+        return out.copy_(o) if out is not None else o
+    if out is None:
+        out = torch.empty(T, y.shape[1], dtype=torch.bfloat16, device=y.device)
+    native().moe_combine(out, y, topk_w.contiguous())
+    return out
+
+
+def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
+            w_down: torch.Tensor, k: int, renorm: bool) -> torch.Tensor:
+    """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
+    SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
+    expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``."""
+    r = moe_route(gate_logits, k, renorm)
+    h = moe_grouped_gemm(x, w_gate_up, r)
+    y = moe_grouped_gemm(h, w_down, r, down=True)
+    return moe_combine(y, r.topk_w)

@@ -13,7 +13,7 @@ Cache layouts are identical to the kernels':
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -365,3 +365,107 @@ def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor
         v = lut[nib].reshape(p.shape[0], K // MXFP4_BLOCK, MXFP4_BLOCK) * s[..., None]
         out[i:i + step] = v.reshape(p.shape[0], K).to(torch.bfloat16)
     return out
+
+
+# ----------------------------------------------------------------------------- sparse MoE
+MOE_MAX_EXPERTS = 256   # csrc/kernels/moe.hip limits
+MOE_MAX_TOPK = 8
+MOE_TILE_ROWS = 32
+
+
+class MoERouting(NamedTuple):
+    """What ``moe_route`` produces for T tokens, E experts, top-k (P = T k (token, slot) pairs,
+    pair index ``t * k + slot``)."""
+
+    topk_ids: torch.Tensor       # [T, k] int32, descending probability
+    topk_w: torch.Tensor         # [T, k] fp32 holding the bf16-rounded weight
+    expert_count: torch.Tensor   # [E] int32
+    expert_offset: torch.Tensor  # [E + 1] int32, exclusive prefix sum of the counts
+    sorted_pairs: torch.Tensor   # [P] int32: pair indices, stably sorted by expert
+    tile_expert: torch.Tensor    # [cap] int32; tile i is rows tile_start[i] .. + tile_rows[i] of
+    tile_start: torch.Tensor     # [cap]        sorted_pairs, all of expert tile_expert[i]
+    tile_rows: torch.Tensor      # [cap]        (1 .. 32 rows); entries past n_tiles are unspecified
+    n_tiles: torch.Tensor        # [1] int32
+
+
+def moe_tile_capacity(T: int, E: int, k: int) -> int:
+    P = T * k
+    return min(E, P) + P // MOE_TILE_ROWS
+
+
+def moe_topk(logits: torch.Tensor, k: int, renorm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HF ``Qwen3MoeTopKRouter`` on ``logits [T, E]`` (bf16): softmax in fp32, the k largest
+    probabilities in descending order, optionally divided by their sum, rounded to bf16.  The
+    selection ranks the logits (softmax is monotone) with a stable sort: ties go to the lower
+    expert index, -0 ranks as +0."""
+    lf = logits.float() + 0.0
+    probs = torch.softmax(lf, dim=-1)
+    ids = torch.sort(lf, dim=-1, descending=True, stable=True).indices[:, :k]
+    w = probs.gather(1, ids)
+    if renorm:
+        w = w / w.sum(dim=-1, keepdim=True)
+    return ids.to(torch.int32), w.to(torch.bfloat16).float()
+
+
+def moe_group(topk_ids: torch.Tensor, E: int):
+    """Group the P pairs of ``topk_ids [T, k]`` by expert: counts, offsets, the stable sort of the
+    pair indices by expert and its cut into tiles of <= 32 rows (ids clamped into [0, E))."""
+    T, k = topk_ids.shape
+    P = T * k
+    dev = topk_ids.device
+    flat = topk_ids.reshape(-1).long().clamp(0, E - 1)
+    count = torch.bincount(flat, minlength=E)
+    offset = torch.zeros(E + 1, dtype=torch.long, device=dev)
+    offset[1:] = count.cumsum(0)
+    sorted_pairs = torch.sort(flat, stable=True).indices
+    ntile = (count + MOE_TILE_ROWS - 1) // MOE_TILE_ROWS
+    tile_expert = torch.repeat_interleave(torch.arange(E, device=dev), ntile)
+    n = tile_expert.numel()
+    first = ntile.cumsum(0) - ntile
+    within = torch.arange(n, device=dev) - first[tile_expert]
+    cap = moe_tile_capacity(T, E, k)
+    tabs = torch.zeros(3, cap, dtype=torch.int32, device=dev)
+    tabs[0, :n] = tile_expert
+    tabs[1, :n] = offset[tile_expert] + MOE_TILE_ROWS * within
+    tabs[2, :n] = torch.clamp(count[tile_expert] - MOE_TILE_ROWS * within, max=MOE_TILE_ROWS)
+    i32 = torch.int32
+    return (count.to(i32), offset.to(i32), sorted_pairs.to(i32), tabs[0], tabs[1], tabs[2],
+            torch.tensor([n], dtype=i32, device=dev))
+
+
+def _swiglu_interleaved(gu: torch.Tensor) -> torch.Tensor:
+    """silu(gate) * up on fp32 products whose columns follow ``ops.swiglu_interleave``'s order:
+    gate and up rounded to bf16 first, the product rounded once (the kernels' epilogue)."""
+    M, n2 = gu.shape
+    v = gu.to(torch.bfloat16).float().reshape(M, n2 // 256, 4, 2, 2, 16)
+    return (F.silu(v[..., 0, :]) * v[..., 1, :]).reshape(M, n2 // 2).to(torch.bfloat16)
+
+
+def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: int,
+                     out: torch.Tensor) -> torch.Tensor:
+    """``epilogue`` 0: ``out[j] = swiglu(x[sorted_pairs[j] // k] . w[e]^T)`` for the rows j of
+    expert e (``w [E, 2I, H]``, rows in ``ops.swiglu_interleave`` order); 1:
+    ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding."""
+    k = r.topk_ids.shape[1]
+    off = r.expert_offset.tolist()
+    pairs = r.sorted_pairs.long()
+    for e in range(w.shape[0]):
+        a, b = off[e], off[e + 1]
+        if a == b:
+            continue
+        wf = w[e].float().t()
+        if epilogue == 0:
+            out[a:b] = _swiglu_interleaved(x[pairs[a:b] // k].float() @ wf)
+        else:
+            out[pairs[a:b]] = (x[a:b].float() @ wf).to(torch.bfloat16)
+    return out
+
+
+def moe_combine(y: torch.Tensor, topk_w: torch.Tensor) -> torch.Tensor:
+    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t k + slot])`` in fp32, in slot order."""
+    T, k = topk_w.shape
+    yv = y[:T * k].view(T, k, -1)
+    acc = torch.zeros(T, yv.shape[-1], dtype=torch.float32, device=y.device)
+    for s in range(k):
+        acc += topk_w[:, s, None] * yv[:, s].float()
+    return acc.to(torch.bfloat16)

@@ -21,7 +21,8 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..config import CacheConfig, KernelPolicy, ModelSpec, ServeConfig, plan_stages, resolve_model
+from ..config import (CacheConfig, KernelPolicy, ModelSpec, ServeConfig, plan_stages,
+                      refuse_moe_quantization, resolve_model)
 from ..models.llama.cache import KVPool
 from ..parallel.pipeline import (DistributedDriver, LocalPipeline, StageFollower, _Channels,
                                  make_transport)
@@ -55,6 +56,8 @@ class EngineConfig:
 def _activation_reserve(spec: ModelSpec, serve: ServeConfig) -> int:
     T = serve.max_num_batched_tokens
     per_tok = 2 * (spec.qkv_size + 3 * spec.intermediate_size + 4 * spec.hidden_size)
+    if spec.num_experts:   # h and y of the grouped expert GEMMs: k rows per token each
+        per_tok += 2 * spec.num_experts_per_tok * (spec.moe_intermediate_size + spec.hidden_size)
     logits = serve.max_batch_size * spec.vocab_size * 4
     return int(T * per_tok * 2 + logits + (2 << 30))
 
@@ -64,6 +67,7 @@ def build_executor(spec: ModelSpec, start: int, end: int, device: torch.device, 
                    kv_share: float = 1.0) -> StageExecutor:
     if cfg.kernels is not None:   # before any weight conversion reads it (int8_transposed)
         ops.set_policy(cfg.kernels)
+    refuse_moe_quantization(spec, cfg.quantize)   # before any weight is built
     stage = build_stage(cfg.checkpoint or spec, start, end, device=device,
                         random_init=cfg.random_init and cfg.checkpoint is None, seed=cfg.seed,
                         quantize=cfg.quantize, checkpoint=cfg.checkpoint,

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""The sparse-MoE MLP on the grouped weight-streaming GEMM (csrc/kernels/moe.hip) measured against
+a loop over the hit experts (docs/kernels.md, "Sparse MoE", quotes the results).
+scripts/bench_mxfp4.py's protocol and helpers.
+
+    python3 scripts/bench_moe.py [--models qwen3-30b-a3b,mixtral-8x7b] [--rows 1,8,64,512] [--out DIR]
+
+Per model (one layer's shapes) and per decode row count T, with random router logits:
+
+``moe``       ops.moe_mlp: routing (top-k + grouping), gate|up + SwiGLU, down, combine -- every
+              count read from device memory, nothing on the host;
+``loop``      the baseline: for each hit expert, index_select its tokens, F.linear, the SwiGLU
+              kernel, F.linear, scale by the router weight, index_add_ in fp32 -- the routing and
+              the per-expert index lists computed on the host beforehand and NOT timed.
+
+Both are captured in one hipGraph over enough layer copies (own weights, own logits) that the
+touched expert weights stream from HBM, replays interleaved, median of 7 rounds.  ``moe`` is also
+split into its launches (route, gate|up, down, combine), each in a graph of its own.  Reported:
+us per layer and expert bytes streamed per second (the hit experts' 3 H I bf16 weights over the
+time).  Results: ``<out>/moe.json`` (default ``profiles/moe``).
+"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bench_mxfp4 as bm  # noqa: E402  (its path set-up makes the package importable too)
+
+
+def bench_model(torch, ops, F, name, rows, res, a):
+    from distributed_llm_inference.config import PRESETS
+    spec = PRESETS[name]
+    dev = torch.device("cuda", 0)
+    H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
+                  spec.num_experts_per_tok)
+    layer_bytes = E * 3 * H * I * 2
+    # at T = 1 only k experts per layer are read: enough copies that even those pass the 256 MB
+    # Infinity Cache between replays
+    copies = 8 if layer_bytes < (2 << 30) else 3
+    gen = torch.Generator(device=dev).manual_seed(1)
+    wgu = [torch.empty(E, 2 * I, H, device=dev, dtype=torch.bfloat16).normal_(0, H ** -0.5, generator=gen)
+           for _ in range(copies)]
+    wd = [torch.empty(E, H, I, device=dev, dtype=torch.bfloat16).normal_(0, I ** -0.5, generator=gen)
+          for _ in range(copies)]
+    for T in rows:
+        x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
+        logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
+                  for _ in range(copies)]
+        routes = [ops.moe_route(lg, k, spec.norm_topk_prob) for lg in logits]
+        hit_total, loops = 0, []
+        for c in range(copies):                      # host-side routing of the baseline: not timed
+            ids, w = routes[c].topk_ids.cpu(), routes[c].topk_w.cpu()
+            per = []
+            for e in ids.unique().tolist():
+                tok, slot = (ids == e).nonzero(as_tuple=True)
+                per.append((e, tok.to(dev), w[tok, slot].to(dev)[:, None]))
+            hit_total += len(per)
+            loops.append(per)
+        hit = hit_total / copies
+        touched = hit * 3 * H * I * 2                 # expert bytes one layer streams
+
+        def moe(c):
+            return ops.moe_mlp(x, logits[c], wgu[c], wd[c], k, spec.norm_topk_prob)
+
+        def loop(c):
+            acc = torch.zeros(T, H, device=dev, dtype=torch.float32)
+            for e, tok, we in loops[c]:
+                h = ops.swiglu_interleaved(F.linear(x.index_select(0, tok), wgu[c][e]))
+                acc.index_add_(0, tok, F.linear(h, wd[c][e]).float() * we)
+            return acc.to(torch.bfloat16)
+
+        err = (moe(0).float() - loop(0).float()).abs().max().item()
+        scale = loop(0).float().abs().max().item()
+        hs = [ops.moe_grouped_gemm(x, wgu[c], routes[c]) for c in range(copies)]
+        ys = [ops.moe_grouped_gemm(hs[c], wd[c], routes[c], down=True) for c in range(copies)]
+        parts = {
+            "route": lambda c: ops.moe_route(logits[c], k, spec.norm_topk_prob),
+            "gate_up": lambda c: ops.moe_grouped_gemm(x, wgu[c], routes[c], out=hs[c]),
+            "down": lambda c: ops.moe_grouped_gemm(hs[c], wd[c], routes[c], down=True, out=ys[c]),
+            "combine": lambda c: ops.moe_combine(ys[c], routes[c].topk_w),
+        }
+        cands = {"moe": moe, "loop": loop, **parts}
+        graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
+                  for n, f in cands.items()}
+        samples = {n: [] for n in cands}
+        for _ in range(7):                            # interleaved: same box, same minute
+            for n in cands:
+                samples[n].append(bm._timed(torch, graphs[n], 10) / copies)
+        row = {"T": T, "hit_experts_per_layer": round(hit, 2), "copies": copies,
+               "expert_MB_touched": round(touched / 1e6, 1),
+               "max_abs_diff_moe_vs_loop": round(err, 4), "max_abs_loop": round(scale, 3)}
+        for n in cands:
+            us = statistics.median(samples[n])
+            row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
+                      "max_us": round(max(samples[n]), 2)}
+        for n in ("moe", "loop"):
+            row[n]["expert_TBps"] = round(touched / row[n]["us"] / 1e6, 3)
+        row["moe_vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        print(f"{name:14s} T={T:4d} hit {hit:6.1f}  moe {row['moe']['us']:9.2f} us "
+              f"({row['moe']['expert_TBps']:.2f} TB/s)  loop {row['loop']['us']:9.2f} us "
+              f"({row['loop']['expert_TBps']:.2f} TB/s)  moe/loop {row['moe_vs_loop']:.3f}  "
+              + "  ".join(f"{n} {row[n]['us']:.1f}" for n in parts), flush=True)
+        bm._save(a, "moe.json", res)
+        del graphs
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--models", default="qwen3-30b-a3b,mixtral-8x7b")
+    ap.add_argument("--rows", default="1,8,64,512")
+    ap.add_argument("--out", default=os.path.join(bm.REPO, "profiles", "moe"))
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    torch = bm._torch()
+    import torch.nn.functional as F
+    from distributed_llm_inference import ops
+    res = {"unit": "us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
+                   "`copies` layers); expert_TBps = the hit experts' bf16 weight bytes / time",
+           "candidates": {"moe": "ops.moe_mlp: moe_route + grouped GEMM x 2 + moe_combine",
+                          "loop": "per hit expert: index_select, F.linear, swiglu, F.linear, "
+                                  "index_add_ (fp32); routing on the host, not timed",
+                          "route / gate_up / down / combine": "moe's launches, each alone"},
+           "models": {}}
+    with torch.no_grad():
+        for name in a.models.split(","):
+            bench_model(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")], res, a)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
