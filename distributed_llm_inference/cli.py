@@ -40,6 +40,9 @@ def _common(ap: argparse.ArgumentParser) -> None:
     wq.add_argument("--fp4", action="store_true",
                     help="MXFP4 weights (4-bit e2m1 + e8m0 scale per 32: 17/32 byte per "
                          "parameter; the interactive-decode and KV-capacity mode)")
+    wq.add_argument("--fp8-experts", action="store_true",
+                    help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
+                         "attention, norms and the router stay bf16")
     ap.add_argument("--int8-threshold", type=float, default=6.0,
                     help="LLM.int8 outlier threshold (bitsandbytes / reference default 6.0 / 5.0)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
@@ -71,8 +74,9 @@ def engine_config(a):
     if getattr(a, "transport", None):
         os.environ["DLI_TRANSPORT"] = a.transport   # read by every rank's make_transport
     quantize = ("fp8" if a.fp8 else "int8" if a.int8
-                else "mxfp4" if getattr(a, "fp4", False) else False)
-    # sparse-MoE models take bf16 weights only: fail here, before any rank is started
+                else "mxfp4" if getattr(a, "fp4", False)
+                else "fp8_experts" if getattr(a, "fp8_experts", False) else False)
+    # sparse-MoE models take bf16 weights or fp8_experts: fail here, before any rank is started
     refuse_moe_quantization(resolve_model(a.checkpoint or a.model), quantize)
     return EngineConfig(
         kernels=KernelPolicy().with_overrides(getattr(a, "kernels", "")),
@@ -106,6 +110,15 @@ def cmd_plan(a) -> int:
     # few thousand bf16 values per layer, are not told apart)
     per_param = 17 / 32 if a.fp4 else (1 if (a.fp8 or a.int8) else 2)
     per_layer = int(spec.layer_param_count() * per_param)
+    if getattr(a, "fp8_experts", False):
+        # experts: a byte per parameter and an fp32 scale per weight row (2 I gate|up rows and H
+        # down rows per expert); the rest of the layer stays bf16
+        if not spec.num_experts:
+            raise ValueError(f"--fp8-experts needs a sparse MoE model; {spec.name} has no experts")
+        rows = spec.num_experts * (2 * spec.moe_intermediate_size + spec.hidden_size)
+        per_layer = (spec.expert_param_count() + 4 * rows
+                     + 2 * (spec.layer_param_count() - spec.expert_param_count()))
+        per_param = per_layer / spec.layer_param_count()
     emb = spec.vocab_size * spec.hidden_size * 2
     replicas = []
     for r in range(layout.dp):

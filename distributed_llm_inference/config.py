@@ -130,6 +130,10 @@ class ModelSpec:
             mlp = h * self.num_experts + self.num_experts * 3 * h * self.moe_intermediate_size
         return h * self.qkv_size + self.q_size * h + mlp + 2 * h + qk
 
+    def expert_param_count(self) -> int:
+        """Per layer: every routed expert's gate, up and down (0 for a dense model)."""
+        return self.num_experts * 3 * self.hidden_size * self.moe_intermediate_size
+
     def param_count(self) -> int:
         emb = self.vocab_size * self.hidden_size
         head = 0 if self.tie_word_embeddings else emb
@@ -403,13 +407,19 @@ PRESETS: Dict[str, ModelSpec] = {
 
 
 def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
-    """Weight quantisation of a sparse-MoE model is an error, not a fallback: the grouped expert
-    GEMM (csrc/kernels/moe.hip) takes bf16 expert weights only."""
-    if spec.num_experts and mode not in (False, None, "none", "bf16"):
+    """Whole-model weight quantisation of a sparse-MoE model is an error, not a fallback: the
+    grouped expert GEMM (csrc/kernels/moe.hip) takes bf16 expert weights, or fp8 ones under the
+    mode of its own, "fp8_experts", which leaves everything but the experts bf16 -- and which a
+    model without experts cannot take."""
+    if mode == "fp8_experts" and not spec.num_experts:
+        raise ValueError(f"fp8_experts needs a sparse MoE model; {spec.name} ({spec.model_type}) "
+                         "has no experts")
+    if spec.num_experts and mode not in (False, None, "none", "bf16", "fp8_experts"):
         mode = "fp8" if mode is True else mode
         raise ValueError(f"{mode} weights are not supported for sparse MoE layers "
                          f"({spec.model_type}, {spec.name}): the grouped expert GEMM takes bf16 "
-                         "expert weights only")
+                         "expert weights, or fp8 expert weights as mode fp8_experts "
+                         "(--fp8-experts)")
 
 
 def resolve_model(model: Any) -> ModelSpec:

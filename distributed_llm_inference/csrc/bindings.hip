@@ -1062,11 +1062,21 @@ void moe_group(Tensor ids, Tensor expert_count, Tensor expert_offset, Tensor sor
 
 // epilogue 0: out h [>= P, I] = swiglu(x[token] . W[e]^T), x [T, K], W [E, 2 I, K];
 // epilogue 1: out y [>= P, N] (row = pair index) = x[start + r] . W[e]^T, x = h [>= P, K], W [E, N, K]
+// W is bf16, or with w_scale [E, N] (fp32, one per weight row) fp8 e4m3fn
 void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor tile_expert,
                       Tensor tile_start, Tensor tile_rows, Tensor n_tiles, int64_t T, int64_t k,
-                      int64_t epilogue) {
+                      int64_t epilogue, optional<Tensor> w_scale) {
   CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
-  CHECK_BF16(out); CHECK_BF16(x); CHECK_BF16(w);
+  CHECK_BF16(out); CHECK_BF16(x);
+  const bool fp8 = w_scale.has_value();
+  if (fp8) {
+    CHECK_IN(*w_scale); CHECK_F32(*w_scale);
+    TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn,
+                "moe_grouped_gemm: w_scale goes with fp8 e4m3fn weights");
+  } else {
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16,
+                "moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with w_scale");
+  }
   TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
               "moe_grouped_gemm: out / x 2-D, w [E, N, K]");
   TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_grouped_gemm: epilogue 0 (gate|up) or 1 (down)");
@@ -1082,6 +1092,18 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
   TORCH_CHECK(out.device() == x.device() && w.device() == x.device(),
               "moe_grouped_gemm: one device");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  if (fp8) {
+    TORCH_CHECK(w_scale->dim() == 2 && w_scale->size(0) == E && w_scale->size(1) == N &&
+                    w_scale->device() == x.device(),
+                "moe_grouped_gemm: w_scale [E, N] on the weights' device");
+    check_rc(dli::launch_moe_grouped_gemm_fp8(
+                 bp(out), bp(x), static_cast<const uint8_t*>(w.data_ptr()),
+                 w_scale->data_ptr<float>(), sorted_pairs.data_ptr<int>(),
+                 tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
+                 tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(), (int)tb.cap, (int)T, (int)E,
+                 (int)k, (int)N, (int)K, (int)epilogue, cur_stream()), "moe_grouped_gemm");
+    return;
+  }
   check_rc(dli::launch_moe_grouped_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
                                         tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
                                         tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(),
@@ -1359,7 +1381,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped weight-streaming MFMA GEMM over the routed experts (0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("tile_expert"), py::arg("tile_start"), py::arg("tile_rows"), py::arg("n_tiles"),
-        py::arg("T"), py::arg("k"), py::arg("epilogue"));
+        py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none());
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"));
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",

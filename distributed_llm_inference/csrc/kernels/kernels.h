@@ -188,6 +188,13 @@ int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* 
                             const int* tile_expert, const int* tile_start, const int* tile_rows,
                             const int* n_tiles, int cap, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream);
+// the same on fp8 weights: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32 (one per weight row, in
+// the rows' stored order), applied to the fp32 accumulator; the activations stay bf16
+int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
+                                const int* sorted_pairs, const int* tile_expert,
+                                const int* tile_start, const int* tile_rows, const int* n_tiles,
+                                int cap, int T, int E, int k, int N, int K, int epilogue,
+                                hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

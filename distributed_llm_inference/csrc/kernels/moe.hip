@@ -1,7 +1,8 @@
-// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral) with bf16 expert weights: routing, a grouped
-// weight-streaming MFMA GEMM over the hit experts, and the weighted combine.  Every grid is fixed
-// by (T, E, k, N) alone and every count is read from device memory, so the launches are
-// hipGraph-capturable and the same launches serve 1 decode row, decode batches and prefill chunks.
+// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral) with bf16 or fp8 (e4m3fn, one fp32 scale per
+// weight row) expert weights: routing, a grouped weight-streaming MFMA GEMM over the hit experts,
+// and the weighted combine.  Every grid is fixed by (T, E, k, N) alone and every count is read
+// from device memory, so the launches are hipGraph-capturable and the same launches serve 1 decode
+// row, decode batches and prefill chunks.
 //
 //   * moe_topk (wave per token).  E <= 256 router logits (bf16) per token.  Softmax is monotone,
 //     so the top-k of the probabilities is the top-k of the logits: every logit becomes an
@@ -38,6 +39,14 @@
 //     Every table value is clamped before it forms an address (expert into [0, E), rows into
 //     [1, 32], start + rows <= P, pair < P hence token < T): a garbage table cannot leave the
 //     buffers.
+//     fp8 weights (WF = kMoeFp8: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32): the same kernel
+//     with gemm_fp8_small.hip's A operand -- lane (r, g) loads the 32 bytes
+//     W8[n0 + 16 a + r][128 t + 32 g .. + 31] as two non-temporal 16-byte loads per A tile and
+//     step, and dwords 2 i, 2 i + 1, widened e4m3 -> bf16 in registers (exact), are its A fragment
+//     of MFMA i: the k order, the wave's steps and the order of the MFMAs are the bf16 variant's.
+//     The activations are never quantised; the scale of weight row n of expert e,
+//     w_scale[e N + n], multiplies the fp32 accumulator after the K-split sum (gate and up each
+//     by their own row's scale before their bf16 rounding).
 //   * moe_combine.  out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order.
 #include "kernels.h"
 
@@ -184,10 +193,15 @@ constexpr int kWaves = 8;              // K-split ways = waves per workgroup
 constexpr int kThreads = kWaves * 64;
 constexpr int kRowsWg = 32;            // weight rows per workgroup: two 16-row A tiles
 constexpr int kTileRows = 32;          // activation rows per tile: two 16-column B tiles
-constexpr int kUnroll = 2;             // k-steps of weight loads in flight per lane
-static_assert(kUnroll % 2 == 0, "a group starts on x buffer 0");
 
 enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
+enum MoeWf { kMoeBf16 = 0, kMoeFp8 = 1 };
+
+// k-steps of weight loads in flight per lane: 8 (bf16) / 4 (fp8) 16-byte loads per step, 16
+// loads in flight either way (fp8 with 2 measured 0-4 % slower: docs/kernels.md)
+template <int WF> constexpr int kUnrollOf = WF == kMoeFp8 ? 4 : 2;
+static_assert(kUnrollOf<kMoeBf16> % 2 == 0 && kUnrollOf<kMoeFp8> % 2 == 0,
+              "a group starts on x buffer 0");
 
 typedef unsigned u32x4m __attribute__((ext_vector_type(4)));   // nontemporal-loadable 16 B
 
@@ -208,12 +222,17 @@ __device__ __forceinline__ int swz(int c) { return c ^ ((c & 4) << 1); }
 __device__ __forceinline__ int clamp_pair(int p, int P) { return min(max(p, 0), P - 1); }
 
 // One tile: `rows` (1 .. 16 MT) activation rows x the 32 weight rows n0 .. n0 + 31 of W [N, K].
-// pairs = sorted_pairs + start.
-template <int MT, int EPI>
+// pairs = sorted_pairs + start.  W is the expert's [N, K] bf16 (WF = kMoeBf16) or e4m3 bytes with
+// its N row scales `wscale` (kMoeFp8).
+template <int MT, int EPI, int WF>
 __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
-                                         const bf16* __restrict__ W, bf16* __restrict__ out,
+                                         const char* __restrict__ W,
+                                         const float* __restrict__ wscale, bf16* __restrict__ out,
                                          const int* __restrict__ pairs, int start, int rows,
                                          int nb, int topk, int P, int N, int K) {
+  constexpr int kWB = WF == kMoeFp8 ? 1 : 2;   // bytes per weight
+  constexpr int kWL = 2 * kWB;                 // 16-byte loads per A tile and k-step
+  constexpr int kUnroll = kUnrollOf<WF>;
   constexpr int kXBuf = MT * 16 * 256;   // one k-step of x: 16 MT rows x 128 bf16
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -223,9 +242,9 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   char* xw = smem + wave * (2 * kXBuf);   // this wave's two x buffers; nobody else touches them
 
   // this lane's weight rows (A tiles 0 / 1; N % 32 == 0: both whole) at its 32-k block of step 0
-  const bf16* wp[2];
+  const char* wp[2];
 #pragma unroll
-  for (int a = 0; a < 2; ++a) wp[a] = W + (size_t)(n0 + 16 * a + r) * K + 32 * g;
+  for (int a = 0; a < 2; ++a) wp[a] = W + ((size_t)(n0 + 16 * a + r) * K + 32 * g) * kWB;
   // x staging: DMA instruction q fills image rows 4 q .. 4 q + 3 (lane l: row 4 q + (l >> 4),
   // slot l & 15) with whole 256-byte row pieces; the slot permutation is on the source address.
   // Image rows past `rows` repeat the tile's last row.
@@ -251,20 +270,20 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
     for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // k-step t < kt: every address below stays inside its row (K % 128 == 0)
-  auto load_w = [&](int t, u32x4m (&wv)[2][4]) {
+  auto load_w = [&](int t, u32x4m (&wv)[2][kWL]) {
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < kWL; ++i)
         wv[a][i] = __builtin_nontemporal_load(
-            reinterpret_cast<const u32x4m*>(wp[a] + (size_t)t * 128 + 8 * i));
+            reinterpret_cast<const u32x4m*>(wp[a] + (size_t)t * (128 * kWB) + 16 * i));
   };
   auto stage_x = [&](int t, int buf) {
 #pragma unroll
     for (int q = 0; q < 4 * MT; ++q)
       glds16(xsrc[q] + (size_t)t * 128, xw + buf * kXBuf + q * 1024);
   };
-  auto step = [&](int buf, const u32x4m (&wv)[2][4]) {
+  auto step = [&](int buf, const u32x4m (&wv)[2][kWL]) {
     bf16x8 xb[MT][4];
 #pragma unroll
     for (int b = 0; b < MT; ++b)
@@ -275,7 +294,11 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
     for (int a = 0; a < 2; ++a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8 wf = __builtin_bit_cast(bf16x8, wv[a][i]);
+        bf16x8 wf;
+        if constexpr (WF == kMoeFp8)   // dwords 2 i, 2 i + 1 of the lane's 8: exact widening
+          wf = fp8x8_to_bf16x8(uint2{wv[a][i >> 1][2 * (i & 1)], wv[a][i >> 1][2 * (i & 1) + 1]});
+        else
+          wf = __builtin_bit_cast(bf16x8, wv[a][i]);
 #pragma unroll
         for (int b = 0; b < MT; ++b)
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb[b][i], acc[a][b], 0, 0, 0);
@@ -291,7 +314,7 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   if (nsteps > 0) stage_x(wave, 0);
   int i = 0;
   for (; i + kUnroll <= nsteps; i += kUnroll) {   // whole groups; kUnroll is even: buffer u & 1
-    u32x4m wv[kUnroll][2][4];
+    u32x4m wv[kUnroll][2][kWL];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) load_w(wave + (i + u) * kWaves, wv[u]);
     asm volatile("" ::: "memory");
@@ -308,7 +331,7 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
     }
   }
   for (; i < nsteps; ++i) {   // fewer than kUnroll steps left
-    u32x4m wv[2][4];
+    u32x4m wv[2][kWL];
     load_w(wave + i * kWaves, wv);
     asm volatile("" ::: "memory");
     if (i + 1 < nsteps) {
@@ -346,6 +369,16 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   }
 
   // ---- epilogue: acc[a][b][e] = y[m = 16 b + r][n = n0 + 16 a + 4 g + e] ----
+  if constexpr (WF == kMoeFp8) {   // the scales of the lane's four weight rows per A tile
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const f32x4 ws = *reinterpret_cast<const f32x4*>(wscale + n0 + 16 * a + 4 * g);
+#pragma unroll
+      for (int b = 0; b < MT; ++b)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[a][b][e] *= ws[e];
+    }
+  }
   if constexpr (EPI == kMoeGateUp) {
     const int I = N >> 1;
     const int col = 16 * nb + 4 * g;
@@ -379,10 +412,10 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   }
 }
 
-template <int EPI>
+template <int EPI, int WF>
 __global__ void __launch_bounds__(kThreads)
-moe_grouped_gemm_kernel(const bf16* __restrict__ x, const bf16* __restrict__ W,
-                        bf16* __restrict__ out, const int* __restrict__ sorted_pairs,
+moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
+                        const float* __restrict__ wscale, bf16* __restrict__ out, const int* __restrict__ sorted_pairs,
                         const int* __restrict__ tile_expert, const int* __restrict__ tile_start,
                         const int* __restrict__ tile_rows, const int* __restrict__ n_tiles,
                         int E, int topk, int P, int N, int K) {
@@ -392,10 +425,13 @@ moe_grouped_gemm_kernel(const bf16* __restrict__ x, const bf16* __restrict__ W,
   const int e = min(max(tile_expert[tile], 0), E - 1);
   const int rows = min(max(tile_rows[tile], 1), min(kTileRows, P));
   const int start = min(max(tile_start[tile], 0), P - rows);
-  const bf16* We = W + (size_t)e * N * K;
+  const char* We = static_cast<const char*>(W) + (size_t)e * N * K * (WF == kMoeFp8 ? 1 : 2);
+  const float* se = WF == kMoeFp8 ? wscale + (size_t)e * N : nullptr;
   const int* pairs = sorted_pairs + start;
-  if (rows <= 16) moe_tile<1, EPI>(smem, x, We, out, pairs, start, rows, nb, topk, P, N, K);
-  else moe_tile<2, EPI>(smem, x, We, out, pairs, start, rows, nb, topk, P, N, K);
+  if (rows <= 16)
+    moe_tile<1, EPI, WF>(smem, x, We, se, out, pairs, start, rows, nb, topk, P, N, K);
+  else
+    moe_tile<2, EPI, WF>(smem, x, We, se, out, pairs, start, rows, nb, topk, P, N, K);
 }
 
 // ------------------------------------------------------------------------------------- combine
@@ -449,25 +485,50 @@ int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int*
   return 0;
 }
 
-int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
-                            const int* tile_expert, const int* tile_start, const int* tile_rows,
-                            const int* n_tiles, int cap, int T, int E, int k, int N, int K,
-                            int epilogue, hipStream_t stream) {
+namespace {
+
+template <int WF>
+int launch_grouped(bf16* out, const bf16* x, const void* W, const float* wscale,
+                   const int* sorted_pairs, const int* tile_expert, const int* tile_start,
+                   const int* tile_rows, const int* n_tiles, int cap, int T, int E, int k, int N,
+                   int K, int epilogue, hipStream_t stream) {
   if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK) return -1;
   if (N <= 0 || N % 32 != 0 || K <= 0 || K % 128 != 0) return -2;
   if (cap <= 0 || cap > 65535 || (long)T * k > (1L << 30)) return -3;
   if (out == nullptr || x == nullptr || W == nullptr) return -5;
+  if (WF == kMoeFp8 && wscale == nullptr) return -5;
   const dim3 grid(N / kRowsWg, cap);
   const int P = T * k;
   if (epilogue == kMoeGateUp)
-    moe_grouped_gemm_kernel<kMoeGateUp><<<grid, kThreads, 0, stream>>>(
-        x, W, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N, K);
+    moe_grouped_gemm_kernel<kMoeGateUp, WF><<<grid, kThreads, 0, stream>>>(
+        x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
+        K);
   else if (epilogue == kMoeDown)
-    moe_grouped_gemm_kernel<kMoeDown><<<grid, kThreads, 0, stream>>>(
-        x, W, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N, K);
+    moe_grouped_gemm_kernel<kMoeDown, WF><<<grid, kThreads, 0, stream>>>(
+        x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
+        K);
   else
     return -4;
   return 0;
+}
+
+}  // namespace
+
+int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+                            const int* tile_expert, const int* tile_start, const int* tile_rows,
+                            const int* n_tiles, int cap, int T, int E, int k, int N, int K,
+                            int epilogue, hipStream_t stream) {
+  return launch_grouped<kMoeBf16>(out, x, W, nullptr, sorted_pairs, tile_expert, tile_start,
+                                  tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+}
+
+int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
+                                const int* sorted_pairs, const int* tile_expert,
+                                const int* tile_start, const int* tile_rows, const int* n_tiles,
+                                int cap, int T, int E, int k, int N, int K, int epilogue,
+                                hipStream_t stream) {
+  return launch_grouped<kMoeFp8>(out, x, W8, w_scale, sorted_pairs, tile_expert, tile_start,
+                                 tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
 }
 
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,

@@ -282,8 +282,10 @@ class MoEMLP(nn.Module):
         out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) # fp32, slot order, one rounding
 
     ``w_gate_up [E, 2I, H]`` holds every expert's rows in ``ops.swiglu_interleave`` order, always
-    (``set_fused_swiglu`` is a no-op); ``w_down [E, H, I]``.  Expert weights are bf16 only.  The
-    block returns a plain bf16 tensor: nothing is deferred to the next RMSNorm."""
+    (``set_fused_swiglu`` is a no-op); ``w_down [E, H, I]``.  Expert weights are bf16, or after
+    :meth:`quantize_experts_fp8` e4m3 with one fp32 scale per weight row (``w_gate_up_scale
+    [E, 2I]``, ``w_down_scale [E, H]``); the router stays bf16 and the activations are never
+    quantised.  The block returns a plain bf16 tensor: nothing is deferred to the next RMSNorm."""
 
     def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16):
         super().__init__()
@@ -301,7 +303,31 @@ class MoEMLP(nn.Module):
                                       requires_grad=False)
         self.w_down = nn.Parameter(torch.empty(E, H, I, dtype=dtype, device=device),
                                    requires_grad=False)
+        self.register_buffer("w_gate_up_scale", None, persistent=False)
+        self.register_buffer("w_down_scale", None, persistent=False)
         self.fused_swiglu = True   # the experts' gate|up rows are always interleaved
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.w_gate_up_scale is not None
+
+    def quantize_experts_fp8(self) -> None:
+        """Expert weights -> fp8 e4m3 with per-row scales (ops.quantize_expert_weights_fp8: one
+        expert at a time), in place of the bf16 tensors, which are freed.  The scale of a gate|up
+        row travels with the row, so the interleaved order is kept."""
+        if self.is_fp8:
+            return
+        for name in ("w_gate_up", "w_down"):
+            w8, scale = ops.quantize_expert_weights_fp8(getattr(self, name).data)
+            setattr(self, name, nn.Parameter(w8, requires_grad=False))
+            setattr(self, name + "_scale", scale)
+
+    def _expert_bf16(self, name: str, e: int) -> torch.Tensor:
+        """Expert e's weight as bf16: the tensor itself, or the dequantised fp8 rows."""
+        w = getattr(self, name)[e]
+        if not self.is_fp8:
+            return w
+        return (w.float() * getattr(self, name + "_scale")[e][:, None]).to(torch.bfloat16)
 
     def set_fused_swiglu(self, on: bool) -> None:
         """No-op: the grouped GEMM's only epilogue reads interleaved rows."""
@@ -310,7 +336,7 @@ class MoEMLP(nn.Module):
         if x_q is not None or norm is not None:
             raise RuntimeError("MoEMLP takes normalised bf16 rows (the layer's generic body)")
         return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
-                           self.norm_topk_prob)
+                           self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale)
 
     # ------------------------------------------------------------------ weights
     def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
@@ -319,6 +345,9 @@ class MoEMLP(nn.Module):
         ``block_sparse_moe.experts.{e}.{w1,w3,w2}.weight`` with w1 = gate, w3 = up, w2 = down), or
         the fused 3-D tensors ``experts.gate_up_proj [E, 2I, H]`` (gate half first) and
         ``experts.down_proj [E, H, I]`` under either prefix."""
+        if self.is_fp8:
+            raise RuntimeError("MoEMLP.load_hf on fp8 experts: load the bf16 weights first, then "
+                               "quantize_experts_fp8()")
         pre = next((p for p in ("mlp.", "block_sparse_moe.") if p + "gate.weight" in sd), None)
         if pre is None:
             g("block_sparse_moe.gate.weight" if self.mixtral_keys else "mlp.gate.weight")
@@ -341,14 +370,15 @@ class MoEMLP(nn.Module):
             self.w_down[e].copy_(down.to(dt))
 
     def hf_dict(self) -> dict:
-        """The hub's per-expert layout (inverse of :meth:`load_hf`)."""
+        """The hub's per-expert layout (inverse of :meth:`load_hf`); fp8 experts as their
+        dequantised weights rounded to bf16."""
         pre, names = (("block_sparse_moe.", ("w1", "w3", "w2")) if self.mixtral_keys else
                       ("mlp.", ("gate_proj", "up_proj", "down_proj")))
         sd = {pre + "gate.weight": self.gate.weight}
         I = self.intermediate_size
         for e in range(self.num_experts):
-            gate, up = ops.swiglu_deinterleave(self.w_gate_up[e]).split([I, I], 0)
-            for n, w in zip(names, (gate, up, self.w_down[e])):
+            gate, up = ops.swiglu_deinterleave(self._expert_bf16("w_gate_up", e)).split([I, I], 0)
+            for n, w in zip(names, (gate, up, self._expert_bf16("w_down", e))):
                 sd[f"{pre}experts.{e}.{n}.weight"] = w
         return sd
 

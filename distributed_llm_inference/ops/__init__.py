@@ -481,6 +481,20 @@ def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q, s.reshape(1, -1).contiguous()
 
 
+def quantize_expert_weights_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Offline fp8 quantisation of stacked expert weights ``[E, N, K]``: :func:`quantize_weight_fp8`'s
+    rule per expert (one scale per stored weight row), one expert at a time so the fp32 temporary
+    is one expert.  Returns ``(w8 [E, N, K] e4m3fn, scale [E, N] fp32)``."""
+    E, N, K = w.shape
+    w8 = torch.empty(E, N, K, dtype=FP8, device=w.device)
+    scale = torch.empty(E, N, dtype=torch.float32, device=w.device)
+    for e in range(E):
+        q, s = quantize_weight_fp8(w[e])
+        w8[e] = q
+        scale[e] = s.reshape(-1)
+    return w8, scale
+
+
 # MXFP4 (OCP MX v1.0): e2m1 elements, one e8m0 power-of-two scale per 32 consecutive k
 MXFP4_BLOCK = ref.MXFP4_BLOCK
 
@@ -1378,21 +1392,34 @@ def moe_route(logits: torch.Tensor, k: int, renorm: bool) -> MoERouting:
 
 
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None,
+                     w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
     ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
     rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
     ``sorted_pairs[j] // k``.  ``down=True``: ``x = h [P, I]``, ``w [E, H, I]``; returns
     ``y [P, H]`` with row j of h at row ``sorted_pairs[j]`` (the pair index).  ``out`` may have
-    more than P rows; the rest are not touched."""
+    more than P rows; the rest are not touched.  With ``w_scale [E, N]`` (fp32) ``w`` is fp8
+    e4m3fn (:func:`quantize_expert_weights_fp8`): the row scale multiplies the fp32 product, the
+    activations stay bf16."""
     T, k = r.topk_ids.shape
     P, N = T * k, w.shape[1]
     if out is None:
         out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=x.device)
     if not _gpu(x):
-        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out)
-    native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
-                              r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0)
+        ok = (w.dtype == torch.bfloat16 if w_scale is None else
+              w.dtype == FP8 and tuple(w_scale.shape) == (w.shape[0], N))
+        if not ok:
+            raise ValueError("moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with "
+                             "w_scale [E, N]")
+        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale)
+    if w_scale is None:
+        native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
+                                  r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0)
+    else:
+        native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
+                                  r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0,
+                                  w_scale)
     return out
 
 
@@ -1410,11 +1437,14 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor,
 
 
 def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
-            w_down: torch.Tensor, k: int, renorm: bool) -> torch.Tensor:
+            w_down: torch.Tensor, k: int, renorm: bool,
+            w_gate_up_scale: Optional[torch.Tensor] = None,
+            w_down_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
     SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
-    expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``."""
+    expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
+    with their row scales ``[E, 2I]`` / ``[E, H]``."""
     r = moe_route(gate_logits, k, renorm)
-    h = moe_grouped_gemm(x, w_gate_up, r)
-    y = moe_grouped_gemm(h, w_down, r, down=True)
+    h = moe_grouped_gemm(x, w_gate_up, r, w_scale=w_gate_up_scale)
+    y = moe_grouped_gemm(h, w_down, r, down=True, w_scale=w_down_scale)
     return moe_combine(y, r.topk_w)

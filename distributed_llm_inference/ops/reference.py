@@ -442,10 +442,11 @@ def _swiglu_interleaved(gu: torch.Tensor) -> torch.Tensor:
 
 
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: int,
-                     out: torch.Tensor) -> torch.Tensor:
+                     out: torch.Tensor, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``epilogue`` 0: ``out[j] = swiglu(x[sorted_pairs[j] // k] . w[e]^T)`` for the rows j of
     expert e (``w [E, 2I, H]``, rows in ``ops.swiglu_interleave`` order); 1:
-    ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding."""
+    ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding.
+    ``w_scale [E, N]``: ``w`` is fp8 and row n of expert e is ``w[e, n] * w_scale[e, n]``."""
     k = r.topk_ids.shape[1]
     off = r.expert_offset.tolist()
     pairs = r.sorted_pairs.long()
@@ -453,7 +454,10 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: 
         a, b = off[e], off[e + 1]
         if a == b:
             continue
-        wf = w[e].float().t()
+        wf = w[e].float()
+        if w_scale is not None:
+            wf = wf * w_scale[e].float()[:, None]
+        wf = wf.t()
         if epilogue == 0:
             out[a:b] = _swiglu_interleaved(x[pairs[a:b] // k].float() @ wf)
         else:

@@ -148,7 +148,8 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
                dtype: torch.dtype = torch.bfloat16, random_init: bool = False,
                seed: int = 0) -> LlamaBlock:
     """Build the block of ``layer_ids`` and load its weights (per layer, only the needed shards).
-    ``use_quantized``: False, True / "fp8", "int8" or "mxfp4" (``apply_quantization``'s modes)."""
+    ``use_quantized``: False, True / "fp8", "int8", "mxfp4" or "fp8_experts"
+    (``apply_quantization``'s modes)."""
     spec = _load_config(model_name, cache_dir, token)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
     block = make_block(spec, layer_ids, device=device, dtype=dtype)
@@ -173,6 +174,8 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
     5.0) computed in bf16 (reference utils/model.py:93-123).  ``quantize="mxfp4"`` (alias
     ``"fp4"``): OCP MX 4-bit e2m1 weights with one e8m0 scale per 32 input features (17/32 byte
     per parameter; Llama-family blocks) — the interactive-decode and capacity mode.
+    ``quantize="fp8_experts"``: sparse-MoE blocks only — the routed experts' weights as fp8 e4m3
+    with one scale per weight row; attention, norms and the router stay bf16.
     """
     if device is None:
         if not torch.cuda.is_available():

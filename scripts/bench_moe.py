@@ -4,6 +4,7 @@ a loop over the hit experts (docs/kernels.md, "Sparse MoE", quotes the results).
 scripts/bench_mxfp4.py's protocol and helpers.
 
     python3 scripts/bench_moe.py [--models qwen3-30b-a3b,mixtral-8x7b] [--rows 1,8,64,512] [--out DIR]
+    python3 scripts/bench_moe.py --fp8 [...]      fp8 expert weights against bf16 -> moe_fp8.json
 
 Per model (one layer's shapes) and per decode row count T, with random router logits:
 
@@ -18,6 +19,12 @@ touched expert weights stream from HBM, replays interleaved, median of 7 rounds.
 split into its launches (route, gate|up, down, combine), each in a graph of its own.  Reported:
 us per layer and expert bytes streamed per second (the hit experts' 3 H I bf16 weights over the
 time).  Results: ``<out>/moe.json`` (default ``profiles/moe``).
+
+``--fp8`` measures fp8 expert weights (ops.quantize_expert_weights_fp8 of the same bf16 tensors)
+against bf16 instead: candidates ``moe`` / ``gate_up`` / ``down`` and ``moe_fp8`` /
+``gate_up_fp8`` / ``down_fp8``, the same graphs over copies, interleaved in the same process.
+Reported per fp8 candidate: TB/s on the fp8 bytes (the hit experts' 3 H I bytes and their 2 I + H
+fp32 row scales) and the time ratio to its bf16 twin.  Results: ``<out>/moe_fp8.json``.
 """
 import argparse
 import os
@@ -38,11 +45,19 @@ def bench_model(torch, ops, F, name, rows, res, a):
     # at T = 1 only k experts per layer are read: enough copies that even those pass the 256 MB
     # Infinity Cache between replays
     copies = 8 if layer_bytes < (2 << 30) else 3
+    if a.fp8 and copies == 8:
+        copies = 16                                   # ... at half the bytes per expert
     gen = torch.Generator(device=dev).manual_seed(1)
     wgu = [torch.empty(E, 2 * I, H, device=dev, dtype=torch.bfloat16).normal_(0, H ** -0.5, generator=gen)
            for _ in range(copies)]
     wd = [torch.empty(E, H, I, device=dev, dtype=torch.bfloat16).normal_(0, I ** -0.5, generator=gen)
           for _ in range(copies)]
+    if a.fp8:
+        q = [(ops.quantize_expert_weights_fp8(wgu[c]), ops.quantize_expert_weights_fp8(wd[c]))
+             for c in range(copies)]
+        wgu8, sgu = [p[0][0] for p in q], [p[0][1] for p in q]
+        wd8, sd = [p[1][0] for p in q], [p[1][1] for p in q]
+        del q
     for T in rows:
         x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
         logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
@@ -81,6 +96,22 @@ def bench_model(torch, ops, F, name, rows, res, a):
             "combine": lambda c: ops.moe_combine(ys[c], routes[c].topk_w),
         }
         cands = {"moe": moe, "loop": loop, **parts}
+        if a.fp8:
+            def moe_fp8(c):
+                return ops.moe_mlp(x, logits[c], wgu8[c], wd8[c], k, spec.norm_topk_prob,
+                                   sgu[c], sd[c])
+
+            h8 = [ops.moe_grouped_gemm(x, wgu8[c], routes[c], w_scale=sgu[c]) for c in range(copies)]
+            y8 = [torch.empty_like(ys[c]) for c in range(copies)]
+            cands = {
+                "moe": moe, "gate_up": parts["gate_up"], "down": parts["down"],
+                "moe_fp8": moe_fp8,
+                "gate_up_fp8": lambda c: ops.moe_grouped_gemm(x, wgu8[c], routes[c], out=h8[c],
+                                                              w_scale=sgu[c]),
+                "down_fp8": lambda c: ops.moe_grouped_gemm(h8[c], wd8[c], routes[c], down=True,
+                                                           out=y8[c], w_scale=sd[c]),
+            }
+            err8 = (moe_fp8(0).float() - moe(0).float()).abs().max().item()
         graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
                   for n, f in cands.items()}
         samples = {n: [] for n in cands}
@@ -94,11 +125,29 @@ def bench_model(torch, ops, F, name, rows, res, a):
             us = statistics.median(samples[n])
             row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
                       "max_us": round(max(samples[n]), 2)}
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        if a.fp8:
+            # bytes of one layer's hit experts: gate|up is 2 / 3 of the weights and 2 I of the rows
+            byt = {"moe": touched, "gate_up": touched * 2 / 3, "down": touched / 3}
+            sc = {"moe": hit * (2 * I + H) * 4, "gate_up": hit * 2 * I * 4, "down": hit * H * 4}
+            row["max_abs_diff_fp8_vs_bf16"] = round(err8, 4)
+            for n in ("moe", "gate_up", "down"):
+                row[n]["expert_TBps"] = round(byt[n] / row[n]["us"] / 1e6, 3)
+                f8 = row[n + "_fp8"]
+                f8["expert_TBps"] = round((byt[n] / 2 + sc[n]) / f8["us"] / 1e6, 3)
+                f8["vs_bf16"] = round(f8["us"] / row[n]["us"], 3)
+            print(f"{name:14s} T={T:4d} hit {hit:6.1f}  " + "  ".join(
+                f"{n} {row[n]['us']:.1f} / fp8 {row[n + '_fp8']['us']:.1f} us "
+                f"({row[n + '_fp8']['expert_TBps']:.2f} TB/s, x{row[n + '_fp8']['vs_bf16']:.3f})"
+                for n in ("moe", "gate_up", "down")), flush=True)
+            bm._save(a, "moe_fp8.json", res)
+            del graphs
+            torch.cuda.empty_cache()
+            continue
         for n in ("moe", "loop"):
             row[n]["expert_TBps"] = round(touched / row[n]["us"] / 1e6, 3)
         row["moe_vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
-        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
-        res["models"][name]["rows"][str(T)] = row
         print(f"{name:14s} T={T:4d} hit {hit:6.1f}  moe {row['moe']['us']:9.2f} us "
               f"({row['moe']['expert_TBps']:.2f} TB/s)  loop {row['loop']['us']:9.2f} us "
               f"({row['loop']['expert_TBps']:.2f} TB/s)  moe/loop {row['moe_vs_loop']:.3f}  "
@@ -113,6 +162,9 @@ def main():
     ap.add_argument("--models", default="qwen3-30b-a3b,mixtral-8x7b")
     ap.add_argument("--rows", default="1,8,64,512")
     ap.add_argument("--out", default=os.path.join(bm.REPO, "profiles", "moe"))
+    ap.add_argument("--fp8", action="store_true",
+                    help="fp8 expert weights against bf16 (moe_fp8.json) instead of moe against loop")
+    ap.add_argument("--note", default="", help="free text kept in the result file (--fp8)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
@@ -125,6 +177,17 @@ def main():
                                   "index_add_ (fp32); routing on the host, not timed",
                           "route / gate_up / down / combine": "moe's launches, each alone"},
            "models": {}}
+    if a.fp8:
+        res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
+                       "`copies` layers); expert_TBps = the hit experts' weight bytes in the "
+                       "candidate's format (fp8: plus their fp32 row scales) / time; vs_bf16 = "
+                       "time / the bf16 twin's time")
+        res["candidates"] = {"moe / gate_up / down": "bf16 expert weights (ops.moe_mlp and its "
+                                                     "two grouped GEMMs alone)",
+                             "moe_fp8 / gate_up_fp8 / down_fp8": "the same on "
+                             "ops.quantize_expert_weights_fp8 of the same tensors"}
+        if a.note:
+            res["note"] = a.note
     with torch.no_grad():
         for name in a.models.split(","):
             bench_model(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")], res, a)
