@@ -42,8 +42,10 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
 
 __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long ctr) {
   const unsigned long long r = splitmix64(seed ^ splitmix64(ctr));
-  // 24 random bits -> (0, 1)
-  return ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);
+  // 23 random bits n -> (n + 0.5) / 2^23, strictly inside (0, 1): 2n + 1 < 2^24, so n + 0.5 is
+  // exact in fp32 (with 24 bits n + 0.5 rounds to even for n >= 2^23 and the largest n gives
+  // 1.0f, an infinite Gumbel term)
+  return ((float)(r >> 41) + 0.5f) * (1.0f / 8388608.0f);
 }
 
 // block argmax of (value, index) pairs; lower index wins ties.
@@ -216,7 +218,9 @@ __device__ __forceinline__ void sample_row_regs(const SampleParams& p, int row, 
   const int k = p.top_k ? p.top_k[row] : 0;
   if (k > 0 && k < V) thr = search(thr, khi, (float)k, false, nullptr);
   const float tp = p.top_p ? p.top_p[row] : 1.f;
-  if (tp < 1.f) {
+  if (!(tp > 0.f)) {
+    thr = (unsigned)kmax;   // top_p <= 0: the maximum value group
+  } else if (tp < 1.f) {
     float z = 0.f;
     thr = search(thr, khi, tp, true, &z);
   }
@@ -275,7 +279,8 @@ __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
   if (!(temp > 0.f)) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    if (!p.logits_is_f32 && V % 8 == 0 && p.row_stride % 8 == 0) {
+    if (!p.logits_is_f32 && V % 8 == 0 && p.row_stride % 8 == 0 &&
+        reinterpret_cast<uintptr_t>(p.logits) % 16 == 0) {
       // bf16 rows: 16-byte loads, 4 in flight per lane (a 128256-wide row is ~16 vectors per
       // lane instead of ~125 dependent 2-byte loads); the argmax is order-independent
       // (lower index wins ties), so the result equals the element-wise loop's
@@ -354,7 +359,10 @@ __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
   }
   // ---------------- top-p (radix select on probability mass) ----------------
   const float tp = p.top_p ? p.top_p[row] : 1.f;
-  if (tp < 1.f) {
+  if (!(tp > 0.f)) {
+    // top_p <= 0: the maximum value group (a target of 0 would select the empty set)
+    thr_key = f2key(mx);
+  } else if (tp < 1.f) {
     float z = 0.f;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
       const float x = load_logit(p, row, i) * inv_t;
@@ -421,7 +429,9 @@ __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
 int launch_sample(const SampleParams& p, int B, hipStream_t stream) {
   if (B == 0) return 0;
   const int n8 = p.V / 8;
-  const bool regs = !p.logits_is_f32 && p.V % 8 == 0 && p.row_stride % 8 == 0;
+  // 16-byte row loads: a [B, V] view may start anywhere in its buffer
+  const bool regs = !p.logits_is_f32 && p.V % 8 == 0 && p.row_stride % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(p.logits) % 16 == 0;
   if (regs && n8 <= 4 * 1024)
     sample_kernel<4><<<B, 1024, 0, stream>>>(p);
   else if (regs && n8 <= 8 * 1024)

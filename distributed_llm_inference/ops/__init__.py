@@ -409,7 +409,8 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
            counters: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``seeds`` + ``counters`` (int64 per row: the sampled token's position in its sequence) key
     each row's randomness, so a seeded request samples the same tokens in any batch / pipeline;
-    without ``counters`` the device ``step`` and the row index do."""
+    without ``counters`` the device ``step`` and the row index do.  ``logits`` may be any
+    [B, V] view with unit column stride; ``top_p <= 0`` keeps the maximum value group."""
     if not _gpu(logits):
         y = ref.sample(logits, temperature, top_k, top_p, generator, seeds=seeds, step=step,
                        counters=counters)

@@ -17,6 +17,7 @@ publisher), and until then every rank just waits.  Here:
 """
 from __future__ import annotations
 
+import atexit
 import collections
 import contextlib
 import json
@@ -166,8 +167,12 @@ class Watchdog:
         self._thread.start()
         return self
 
-    def stop(self) -> None:
+    def stop(self, join_s: float = 0.0) -> None:
+        """End the polling thread; with ``join_s`` wait for it to leave its store call."""
         self._stop.set()
+        t = self._thread
+        if join_s > 0 and t.is_alive() and t is not threading.current_thread():
+            t.join(join_s)
 
     def abort(self, reason: str) -> None:
         """Raise the job-wide alarm (this rank failed or saw a stall) and leave."""
@@ -253,6 +258,11 @@ def start_watchdog(job: str, world: int, on_abort=None) -> Optional[Watchdog]:
     global _WATCHDOG
     if _WATCHDOG is None and float(os.environ.get("DLI_WATCHDOG_S", 90)) > 0:
         _WATCHDOG = Watchdog(job, world, on_abort=on_abort).start()
+        # An orderly exit joins the thread first.  A daemon thread that comes back from the
+        # store's C++ client (which drops the GIL) while the interpreter finalises is ended
+        # inside that C++ frame, and the forced unwind aborts the process ("terminate called
+        # without an active exception") after the rank has done all its work.
+        atexit.register(_WATCHDOG.stop, 15.0)
     return _WATCHDOG
 
 
