@@ -43,6 +43,10 @@ def _common(ap: argparse.ArgumentParser) -> None:
     wq.add_argument("--fp8-experts", action="store_true",
                     help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
                          "attention, norms and the router stay bf16")
+    wq.add_argument("--fp4-experts", action="store_true",
+                    help="sparse-MoE models: MXFP4 expert weights (4-bit e2m1 + e8m0 scale per 32: "
+                         "17/32 byte per expert parameter); attention, norms and the router stay "
+                         "bf16")
     ap.add_argument("--int8-threshold", type=float, default=6.0,
                     help="LLM.int8 outlier threshold (bitsandbytes / reference default 6.0 / 5.0)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
@@ -75,8 +79,10 @@ def engine_config(a):
         os.environ["DLI_TRANSPORT"] = a.transport   # read by every rank's make_transport
     quantize = ("fp8" if a.fp8 else "int8" if a.int8
                 else "mxfp4" if getattr(a, "fp4", False)
-                else "fp8_experts" if getattr(a, "fp8_experts", False) else False)
-    # sparse-MoE models take bf16 weights or fp8_experts: fail here, before any rank is started
+                else "fp8_experts" if getattr(a, "fp8_experts", False)
+                else "mxfp4_experts" if getattr(a, "fp4_experts", False) else False)
+    # sparse-MoE models take bf16 weights, fp8_experts or mxfp4_experts: fail here, before any rank
+    # is started
     refuse_moe_quantization(resolve_model(a.checkpoint or a.model), quantize)
     return EngineConfig(
         kernels=KernelPolicy().with_overrides(getattr(a, "kernels", "")),
@@ -118,6 +124,15 @@ def cmd_plan(a) -> int:
         rows = spec.num_experts * (2 * spec.moe_intermediate_size + spec.hidden_size)
         per_layer = (spec.expert_param_count() + 4 * rows
                      + 2 * (spec.layer_param_count() - spec.expert_param_count()))
+        per_param = per_layer / spec.layer_param_count()
+    if getattr(a, "fp4_experts", False):
+        # experts: K / 2 nibble bytes and K / 32 scale bytes per stored weight row (2 I gate|up
+        # rows of K = H and H down rows of K = I per expert); the rest of the layer stays bf16
+        if not spec.num_experts:
+            raise ValueError(f"--fp4-experts needs a sparse MoE model; {spec.name} has no experts")
+        H, I = spec.hidden_size, spec.moe_intermediate_size
+        experts = spec.num_experts * (2 * I * (H // 2 + H // 32) + H * (I // 2 + I // 32))
+        per_layer = experts + 2 * (spec.layer_param_count() - spec.expert_param_count())
         per_param = per_layer / spec.layer_param_count()
     emb = spec.vocab_size * spec.hidden_size * 2
     replicas = []

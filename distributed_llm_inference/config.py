@@ -409,17 +409,19 @@ PRESETS: Dict[str, ModelSpec] = {
 def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
     """Whole-model weight quantisation of a sparse-MoE model is an error, not a fallback: the
     grouped expert GEMM (csrc/kernels/moe.hip) takes bf16 expert weights, or fp8 ones under the
-    mode of its own, "fp8_experts", which leaves everything but the experts bf16 -- and which a
-    model without experts cannot take."""
-    if mode == "fp8_experts" and not spec.num_experts:
-        raise ValueError(f"fp8_experts needs a sparse MoE model; {spec.name} ({spec.model_type}) "
+    mode of its own, "fp8_experts", or MXFP4 ones under "mxfp4_experts", which leave everything
+    but the experts bf16 -- and which a model without experts cannot take."""
+    if mode in ("fp8_experts", "mxfp4_experts") and not spec.num_experts:
+        raise ValueError(f"{mode} needs a sparse MoE model; {spec.name} ({spec.model_type}) "
                          "has no experts")
-    if spec.num_experts and mode not in (False, None, "none", "bf16", "fp8_experts"):
+    if spec.num_experts and mode not in (False, None, "none", "bf16", "fp8_experts",
+                                         "mxfp4_experts"):
         mode = "fp8" if mode is True else mode
         raise ValueError(f"{mode} weights are not supported for sparse MoE layers "
                          f"({spec.model_type}, {spec.name}): the grouped expert GEMM takes bf16 "
                          "expert weights, or fp8 expert weights as mode fp8_experts "
-                         "(--fp8-experts)")
+                         "(--fp8-experts), or MXFP4 expert weights as mode mxfp4_experts "
+                         "(--fp4-experts)")
 
 
 def resolve_model(model: Any) -> ModelSpec:

@@ -1062,25 +1062,34 @@ void moe_group(Tensor ids, Tensor expert_count, Tensor expert_offset, Tensor sor
 
 // epilogue 0: out h [>= P, I] = swiglu(x[token] . W[e]^T), x [T, K], W [E, 2 I, K];
 // epilogue 1: out y [>= P, N] (row = pair index) = x[start + r] . W[e]^T, x = h [>= P, K], W [E, N, K]
-// W is bf16, or with w_scale [E, N] (fp32, one per weight row) fp8 e4m3fn
+// W is bf16, or with w_scale [E, N] (fp32, one per weight row) fp8 e4m3fn, or with w_block_scale
+// [E, N, K / 32] (e8m0 bytes, one per 32 k) MXFP4 nibbles uint8 [E, N, K / 2]
 void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor tile_expert,
                       Tensor tile_start, Tensor tile_rows, Tensor n_tiles, int64_t T, int64_t k,
-                      int64_t epilogue, optional<Tensor> w_scale) {
+                      int64_t epilogue, optional<Tensor> w_scale,
+                      optional<Tensor> w_block_scale) {
   CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
   CHECK_BF16(out); CHECK_BF16(x);
   const bool fp8 = w_scale.has_value();
-  if (fp8) {
+  const bool fp4 = w_block_scale.has_value();
+  TORCH_CHECK(!(fp8 && fp4), "moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both");
+  if (fp4) {
+    CHECK_IN(*w_block_scale);
+    TORCH_CHECK(w.scalar_type() == at::kByte && w_block_scale->scalar_type() == at::kByte,
+                "moe_grouped_gemm: w_block_scale (uint8) goes with uint8 MXFP4 weights");
+  } else if (fp8) {
     CHECK_IN(*w_scale); CHECK_F32(*w_scale);
     TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn,
                 "moe_grouped_gemm: w_scale goes with fp8 e4m3fn weights");
   } else {
     TORCH_CHECK(w.scalar_type() == at::kBFloat16,
-                "moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with w_scale");
+                "moe_grouped_gemm: bf16 weights, fp8 e4m3fn weights with w_scale, or uint8 MXFP4 "
+                "weights with w_block_scale");
   }
   TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
               "moe_grouped_gemm: out / x 2-D, w [E, N, K]");
   TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_grouped_gemm: epilogue 0 (gate|up) or 1 (down)");
-  const int64_t E = w.size(0), N = w.size(1), K = w.size(2);
+  const int64_t E = w.size(0), N = w.size(1), K = fp4 ? 2 * w.size(2) : w.size(2);
   const MoeTables tb = check_moe_tables(sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles,
                                         T, E, k, x.device(), "moe_grouped_gemm");
   TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "moe_grouped_gemm: needs K % 128 == 0");
@@ -1092,6 +1101,19 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
   TORCH_CHECK(out.device() == x.device() && w.device() == x.device(),
               "moe_grouped_gemm: one device");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  if (fp4) {
+    TORCH_CHECK(w_block_scale->dim() == 3 && w_block_scale->size(0) == E &&
+                    w_block_scale->size(1) == N && w_block_scale->size(2) == K / 32 &&
+                    w_block_scale->device() == x.device(),
+                "moe_grouped_gemm: w_block_scale [E, N, K / 32] on the weights' device");
+    check_rc(dli::launch_moe_grouped_gemm_fp4(
+                 bp(out), bp(x), w.data_ptr<uint8_t>(), w_block_scale->data_ptr<uint8_t>(),
+                 sorted_pairs.data_ptr<int>(), tile_expert.data_ptr<int>(),
+                 tile_start.data_ptr<int>(), tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(),
+                 (int)tb.cap, (int)T, (int)E, (int)k, (int)N, (int)K, (int)epilogue, cur_stream()),
+             "moe_grouped_gemm");
+    return;
+  }
   if (fp8) {
     TORCH_CHECK(w_scale->dim() == 2 && w_scale->size(0) == E && w_scale->size(1) == N &&
                     w_scale->device() == x.device(),
@@ -1381,7 +1403,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped weight-streaming MFMA GEMM over the routed experts (0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("tile_expert"), py::arg("tile_start"), py::arg("tile_rows"), py::arg("n_tiles"),
-        py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none());
+        py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none(),
+        py::arg("w_block_scale") = py::none());
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"));
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",

@@ -195,6 +195,14 @@ int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, con
                                 const int* tile_start, const int* tile_rows, const int* n_tiles,
                                 int cap, int T, int E, int k, int N, int K, int epilogue,
                                 hipStream_t stream);
+// the same on MXFP4 weights: W4 [E, N, K / 2] e2m1 nibbles (element 2 j in the low nibble of byte
+// j), bscale [E, N, K / 32] e8m0 bytes (one per 32 k of a stored weight row), spent in the exact
+// widening to bf16: no epilogue scale; the activations stay bf16
+int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
+                                const int* sorted_pairs, const int* tile_expert,
+                                const int* tile_start, const int* tile_rows, const int* n_tiles,
+                                int cap, int T, int E, int k, int N, int K, int epilogue,
+                                hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

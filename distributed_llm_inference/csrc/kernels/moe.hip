@@ -1,8 +1,8 @@
-// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral) with bf16 or fp8 (e4m3fn, one fp32 scale per
-// weight row) expert weights: routing, a grouped weight-streaming MFMA GEMM over the hit experts,
-// and the weighted combine.  Every grid is fixed by (T, E, k, N) alone and every count is read
-// from device memory, so the launches are hipGraph-capturable and the same launches serve 1 decode
-// row, decode batches and prefill chunks.
+// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral) with bf16, fp8 (e4m3fn, one fp32 scale per
+// weight row) or MXFP4 (e2m1 nibbles, one e8m0 scale per 32 k) expert weights: routing, a grouped
+// weight-streaming MFMA GEMM over the hit experts, and the weighted combine.  Every grid is fixed
+// by (T, E, k, N) alone and every count is read from device memory, so the launches are
+// hipGraph-capturable and the same launches serve 1 decode row, decode batches and prefill chunks.
 //
 //   * moe_topk (wave per token).  E <= 256 router logits (bf16) per token.  Softmax is monotone,
 //     so the top-k of the probabilities is the top-k of the logits: every logit becomes an
@@ -47,6 +47,16 @@
 //     The activations are never quantised; the scale of weight row n of expert e,
 //     w_scale[e N + n], multiplies the fp32 accumulator after the K-split sum (gate and up each
 //     by their own row's scale before their bf16 rounding).
+//     MXFP4 weights (WF = kMoeFp4: W4 [E, N, K / 2] bytes, element 2 j in the low nibble of byte
+//     j, bscale [E, N, K / 32] e8m0 bytes): the same kernel with gemm_fp4_small.hip's A operand --
+//     lane (r, g) loads the 16 bytes W4[n0 + 16 a + r][64 t + 16 g .. + 15] = W[..][128 t + 32 g
+//     .. + 31] as one non-temporal 16-byte load per A tile and step, exactly one scale block, and
+//     the block's byte bscale[n0 + 16 a + r][4 t + g]; dword i, widened e2m1 -> bf16 in registers
+//     with the block's 2^(byte - 127) (v_cvt_scalef32_pk_bf16_fp4, exact), is its A fragment of
+//     MFMA i: again the k order, the wave's steps and the order of the MFMAs are the bf16
+//     variant's, so the result is the bf16 kernel's on the dequantised weights bit for bit.  The
+//     scale is spent in the widening: nothing is left for the epilogue, and the activations are
+//     never quantised.
 //   * moe_combine.  out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order.
 #include "kernels.h"
 
@@ -195,12 +205,15 @@ constexpr int kRowsWg = 32;            // weight rows per workgroup: two 16-row 
 constexpr int kTileRows = 32;          // activation rows per tile: two 16-column B tiles
 
 enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
-enum MoeWf { kMoeBf16 = 0, kMoeFp8 = 1 };
+enum MoeWf { kMoeBf16 = 0, kMoeFp8 = 1, kMoeFp4 = 2 };
 
 // k-steps of weight loads in flight per lane: 8 (bf16) / 4 (fp8) 16-byte loads per step, 16
-// loads in flight either way (fp8 with 2 measured 0-4 % slower: docs/kernels.md)
+// loads in flight either way (fp8 with 2 measured 0-4 % slower: docs/kernels.md); fp4 has 2
+// 16-byte loads and 2 scale bytes per step: 4 + 4 in flight with 2, which measured 0-7 % faster
+// than 4 and 8 at 1-16 rows and 4-5 % slower than 4 at Mixtral's 128 / 512 rows (docs/kernels.md)
 template <int WF> constexpr int kUnrollOf = WF == kMoeFp8 ? 4 : 2;
-static_assert(kUnrollOf<kMoeBf16> % 2 == 0 && kUnrollOf<kMoeFp8> % 2 == 0,
+static_assert(kUnrollOf<kMoeBf16> % 2 == 0 && kUnrollOf<kMoeFp8> % 2 == 0 &&
+                  kUnrollOf<kMoeFp4> % 2 == 0,
               "a group starts on x buffer 0");
 
 typedef unsigned u32x4m __attribute__((ext_vector_type(4)));   // nontemporal-loadable 16 B
@@ -219,19 +232,30 @@ __device__ __forceinline__ void wait_vm() {
 // the 16-byte slot of chunk ch of x row c in the staged image is ch ^ swz(c)
 __device__ __forceinline__ int swz(int c) { return c ^ ((c & 4) << 1); }
 
+// one dword = 8 e2m1 nibbles (element 2 b, 2 b + 1 in byte b) -> 8 bf16, scaled by s (exact)
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(unsigned d, float s) {
+  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0);
+  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1);
+  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2);
+  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
 __device__ __forceinline__ int clamp_pair(int p, int P) { return min(max(p, 0), P - 1); }
 
 // One tile: `rows` (1 .. 16 MT) activation rows x the 32 weight rows n0 .. n0 + 31 of W [N, K].
-// pairs = sorted_pairs + start.  W is the expert's [N, K] bf16 (WF = kMoeBf16) or e4m3 bytes with
-// its N row scales `wscale` (kMoeFp8).
+// pairs = sorted_pairs + start.  W is the expert's [N, K] bf16 (WF = kMoeBf16), e4m3 bytes with
+// its N row scales `wscale` (fp32, kMoeFp8) or [N, K / 2] MXFP4 bytes with its [N, K / 32] e8m0
+// block scales `wscale` (bytes, kMoeFp4).
 template <int MT, int EPI, int WF>
 __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
                                          const char* __restrict__ W,
-                                         const float* __restrict__ wscale, bf16* __restrict__ out,
+                                         const void* __restrict__ wscale, bf16* __restrict__ out,
                                          const int* __restrict__ pairs, int start, int rows,
                                          int nb, int topk, int P, int N, int K) {
-  constexpr int kWB = WF == kMoeFp8 ? 1 : 2;   // bytes per weight
-  constexpr int kWL = 2 * kWB;                 // 16-byte loads per A tile and k-step
+  constexpr int kWB = WF == kMoeBf16 ? 2 : 1;   // bytes per weight (kMoeFp4: half a byte, below)
+  constexpr int kWL = WF == kMoeFp4 ? 1 : 2 * kWB;   // 16-byte loads per A tile and k-step
+  constexpr int kStepB = 16 * 4 * kWL;         // bytes of a weight row per k-step: 4 lanes' loads
   constexpr int kUnroll = kUnrollOf<WF>;
   constexpr int kXBuf = MT * 16 * 256;   // one k-step of x: 16 MT rows x 128 bf16
   const int lane = threadIdx.x & 63;
@@ -242,9 +266,20 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   char* xw = smem + wave * (2 * kXBuf);   // this wave's two x buffers; nobody else touches them
 
   // this lane's weight rows (A tiles 0 / 1; N % 32 == 0: both whole) at its 32-k block of step 0
+  // (kMoeFp4: a row is K / 2 bytes, and the lane's scale byte of step 0 is block g of its row)
   const char* wp[2];
+  const uint8_t* sp[2];
 #pragma unroll
-  for (int a = 0; a < 2; ++a) wp[a] = W + ((size_t)(n0 + 16 * a + r) * K + 32 * g) * kWB;
+  for (int a = 0; a < 2; ++a) {
+    const size_t n = (size_t)(n0 + 16 * a + r);
+    if constexpr (WF == kMoeFp4) {
+      wp[a] = W + n * (size_t)(K >> 1) + 16 * g;
+      sp[a] = static_cast<const uint8_t*>(wscale) + n * (size_t)(K >> 5) + g;
+    } else {
+      wp[a] = W + (n * K + 32 * g) * kWB;
+      sp[a] = nullptr;
+    }
+  }
   // x staging: DMA instruction q fills image rows 4 q .. 4 q + 3 (lane l: row 4 q + (l >> 4),
   // slot l & 15) with whole 256-byte row pieces; the slot permutation is on the source address.
   // Image rows past `rows` repeat the tile's last row.
@@ -270,20 +305,24 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
     for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // k-step t < kt: every address below stays inside its row (K % 128 == 0)
-  auto load_w = [&](int t, u32x4m (&wv)[2][kWL]) {
+  // kMoeFp4: the scale bytes are vector memory loads too, issued here with the weight loads,
+  // i.e. before the next stage_x -- so "all but the 4 MT newest" below still covers them
+  auto load_w = [&](int t, u32x4m (&wv)[2][kWL], unsigned (&sc)[2]) {
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a) {
 #pragma unroll
       for (int i = 0; i < kWL; ++i)
         wv[a][i] = __builtin_nontemporal_load(
-            reinterpret_cast<const u32x4m*>(wp[a] + (size_t)t * (128 * kWB) + 16 * i));
+            reinterpret_cast<const u32x4m*>(wp[a] + (size_t)t * kStepB + 16 * i));
+      if constexpr (WF == kMoeFp4) sc[a] = sp[a][(size_t)t * 4];
+    }
   };
   auto stage_x = [&](int t, int buf) {
 #pragma unroll
     for (int q = 0; q < 4 * MT; ++q)
       glds16(xsrc[q] + (size_t)t * 128, xw + buf * kXBuf + q * 1024);
   };
-  auto step = [&](int buf, const u32x4m (&wv)[2][kWL]) {
+  auto step = [&](int buf, const u32x4m (&wv)[2][kWL], const unsigned (&sc)[2]) {
     bf16x8 xb[MT][4];
 #pragma unroll
     for (int b = 0; b < MT; ++b)
@@ -292,10 +331,14 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
         xb[b][i] = *reinterpret_cast<const bf16x8*>(xw + buf * kXBuf + b * 4096 + xoff[i]);
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
+      float s = 0.f;   // kMoeFp4: 2^(byte - 127), byte in [1, 254]
+      if constexpr (WF == kMoeFp4) s = __uint_as_float(sc[a] << 23);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         bf16x8 wf;
-        if constexpr (WF == kMoeFp8)   // dwords 2 i, 2 i + 1 of the lane's 8: exact widening
+        if constexpr (WF == kMoeFp4)   // dword i of the lane's 4: exact widening
+          wf = fp4x8_to_bf16x8(wv[a][0][i], s);
+        else if constexpr (WF == kMoeFp8)   // dwords 2 i, 2 i + 1 of the lane's 8: exact widening
           wf = fp8x8_to_bf16x8(uint2{wv[a][i >> 1][2 * (i & 1)], wv[a][i >> 1][2 * (i & 1) + 1]});
         else
           wf = __builtin_bit_cast(bf16x8, wv[a][i]);
@@ -315,8 +358,9 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   int i = 0;
   for (; i + kUnroll <= nsteps; i += kUnroll) {   // whole groups; kUnroll is even: buffer u & 1
     u32x4m wv[kUnroll][2][kWL];
+    unsigned sc[kUnroll][2];
 #pragma unroll
-    for (int u = 0; u < kUnroll; ++u) load_w(wave + (i + u) * kWaves, wv[u]);
+    for (int u = 0; u < kUnroll; ++u) load_w(wave + (i + u) * kWaves, wv[u], sc[u]);
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
@@ -326,13 +370,14 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
       } else {
         wait_vm<0>();
       }
-      step(u & 1, wv[u]);
+      step(u & 1, wv[u], sc[u]);
       asm volatile("" ::: "memory");   // the next DMA into this buffer stays behind its reads
     }
   }
   for (; i < nsteps; ++i) {   // fewer than kUnroll steps left
     u32x4m wv[2][kWL];
-    load_w(wave + i * kWaves, wv);
+    unsigned sc[2];
+    load_w(wave + i * kWaves, wv, sc);
     asm volatile("" ::: "memory");
     if (i + 1 < nsteps) {
       stage_x(wave + (i + 1) * kWaves, (i + 1) & 1);
@@ -340,7 +385,7 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
     } else {
       wait_vm<0>();
     }
-    step(i & 1, wv);
+    step(i & 1, wv, sc);
     asm volatile("" ::: "memory");
   }
 
@@ -372,7 +417,8 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
   if constexpr (WF == kMoeFp8) {   // the scales of the lane's four weight rows per A tile
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-      const f32x4 ws = *reinterpret_cast<const f32x4*>(wscale + n0 + 16 * a + 4 * g);
+      const f32x4 ws = *reinterpret_cast<const f32x4*>(static_cast<const float*>(wscale) + n0 +
+                                                       16 * a + 4 * g);
 #pragma unroll
       for (int b = 0; b < MT; ++b)
 #pragma unroll
@@ -415,7 +461,8 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
 template <int EPI, int WF>
 __global__ void __launch_bounds__(kThreads)
 moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
-                        const float* __restrict__ wscale, bf16* __restrict__ out, const int* __restrict__ sorted_pairs,
+                        const void* __restrict__ wscale, bf16* __restrict__ out,
+                        const int* __restrict__ sorted_pairs,
                         const int* __restrict__ tile_expert, const int* __restrict__ tile_start,
                         const int* __restrict__ tile_rows, const int* __restrict__ n_tiles,
                         int E, int topk, int P, int N, int K) {
@@ -425,8 +472,14 @@ moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
   const int e = min(max(tile_expert[tile], 0), E - 1);
   const int rows = min(max(tile_rows[tile], 1), min(kTileRows, P));
   const int start = min(max(tile_start[tile], 0), P - rows);
-  const char* We = static_cast<const char*>(W) + (size_t)e * N * K * (WF == kMoeFp8 ? 1 : 2);
-  const float* se = WF == kMoeFp8 ? wscale + (size_t)e * N : nullptr;
+  // expert e's weights and scales: N rows of 2 K (bf16), K (fp8) or K / 2 (fp4) bytes; N fp32
+  // row scales (fp8) or N K / 32 block-scale bytes (fp4)
+  const size_t wrow = WF == kMoeFp4 ? (size_t)(K >> 1) : (size_t)K * (WF == kMoeFp8 ? 1 : 2);
+  const char* We = static_cast<const char*>(W) + (size_t)e * N * wrow;
+  const void* se = nullptr;
+  if constexpr (WF == kMoeFp8) se = static_cast<const float*>(wscale) + (size_t)e * N;
+  if constexpr (WF == kMoeFp4)
+    se = static_cast<const uint8_t*>(wscale) + (size_t)e * N * (size_t)(K >> 5);
   const int* pairs = sorted_pairs + start;
   if (rows <= 16)
     moe_tile<1, EPI, WF>(smem, x, We, se, out, pairs, start, rows, nb, topk, P, N, K);
@@ -488,7 +541,7 @@ int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int*
 namespace {
 
 template <int WF>
-int launch_grouped(bf16* out, const bf16* x, const void* W, const float* wscale,
+int launch_grouped(bf16* out, const bf16* x, const void* W, const void* wscale,
                    const int* sorted_pairs, const int* tile_expert, const int* tile_start,
                    const int* tile_rows, const int* n_tiles, int cap, int T, int E, int k, int N,
                    int K, int epilogue, hipStream_t stream) {
@@ -496,7 +549,7 @@ int launch_grouped(bf16* out, const bf16* x, const void* W, const float* wscale,
   if (N <= 0 || N % 32 != 0 || K <= 0 || K % 128 != 0) return -2;
   if (cap <= 0 || cap > 65535 || (long)T * k > (1L << 30)) return -3;
   if (out == nullptr || x == nullptr || W == nullptr) return -5;
-  if (WF == kMoeFp8 && wscale == nullptr) return -5;
+  if (WF != kMoeBf16 && wscale == nullptr) return -5;
   const dim3 grid(N / kRowsWg, cap);
   const int P = T * k;
   if (epilogue == kMoeGateUp)
@@ -528,6 +581,15 @@ int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, con
                                 int cap, int T, int E, int k, int N, int K, int epilogue,
                                 hipStream_t stream) {
   return launch_grouped<kMoeFp8>(out, x, W8, w_scale, sorted_pairs, tile_expert, tile_start,
+                                 tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+}
+
+int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
+                                const int* sorted_pairs, const int* tile_expert,
+                                const int* tile_start, const int* tile_rows, const int* n_tiles,
+                                int cap, int T, int E, int k, int N, int K, int epilogue,
+                                hipStream_t stream) {
+  return launch_grouped<kMoeFp4>(out, x, W4, bscale, sorted_pairs, tile_expert, tile_start,
                                  tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
 }
 

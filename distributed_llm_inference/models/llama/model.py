@@ -115,6 +115,16 @@ class LlamaBlock(nn.Module):
             layer.mlp.quantize_experts_fp8()
         return self
 
+    def quantize_experts_mxfp4(self) -> "LlamaBlock":
+        """MXFP4 (e2m1, one e8m0 scale per 32 input features) weights for the routed experts of
+        every sparse-MoE layer; attention projections, norms and the router stay bf16."""
+        if not self.config.num_experts:
+            raise ValueError(f"mxfp4_experts needs a sparse MoE model; {self.config.name} "
+                             f"({self.config.model_type}) has no experts")
+        for layer in self.layers:
+            layer.mlp.quantize_experts_mxfp4()
+        return self
+
     def new_cache(self, window_length: int = 0, num_sink_tokens: int = 0, num_blocks: int = 256,
                   block_size: int = 64) -> PartialLlamaSinkCache:
         c = PartialLlamaSinkCache(window_length, num_sink_tokens, num_blocks, block_size)

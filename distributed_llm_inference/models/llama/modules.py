@@ -284,8 +284,11 @@ class MoEMLP(nn.Module):
     ``w_gate_up [E, 2I, H]`` holds every expert's rows in ``ops.swiglu_interleave`` order, always
     (``set_fused_swiglu`` is a no-op); ``w_down [E, H, I]``.  Expert weights are bf16, or after
     :meth:`quantize_experts_fp8` e4m3 with one fp32 scale per weight row (``w_gate_up_scale
-    [E, 2I]``, ``w_down_scale [E, H]``); the router stays bf16 and the activations are never
-    quantised.  The block returns a plain bf16 tensor: nothing is deferred to the next RMSNorm."""
+    [E, 2I]``, ``w_down_scale [E, H]``), or after :meth:`quantize_experts_mxfp4` MXFP4 nibbles
+    ``[E, 2I, H / 2]`` / ``[E, H, I / 2]`` with one e8m0 scale per 32 input features
+    (``w_gate_up_block_scale [E, 2I, H / 32]``, ``w_down_block_scale [E, H, I / 32]``); the router
+    stays bf16 and the activations are never quantised.  The block returns a plain bf16 tensor:
+    nothing is deferred to the next RMSNorm."""
 
     def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16):
         super().__init__()
@@ -305,6 +308,8 @@ class MoEMLP(nn.Module):
                                    requires_grad=False)
         self.register_buffer("w_gate_up_scale", None, persistent=False)
         self.register_buffer("w_down_scale", None, persistent=False)
+        self.register_buffer("w_gate_up_block_scale", None, persistent=False)
+        self.register_buffer("w_down_block_scale", None, persistent=False)
         self.fused_swiglu = True   # the experts' gate|up rows are always interleaved
 
     @property
@@ -317,14 +322,36 @@ class MoEMLP(nn.Module):
         row travels with the row, so the interleaved order is kept."""
         if self.is_fp8:
             return
+        if self.is_mxfp4:
+            raise ValueError("quantize_experts_fp8: the experts are MXFP4 already")
         for name in ("w_gate_up", "w_down"):
             w8, scale = ops.quantize_expert_weights_fp8(getattr(self, name).data)
             setattr(self, name, nn.Parameter(w8, requires_grad=False))
             setattr(self, name + "_scale", scale)
 
+    @property
+    def is_mxfp4(self) -> bool:
+        return self.w_gate_up_block_scale is not None
+
+    def quantize_experts_mxfp4(self) -> None:
+        """Expert weights -> MXFP4 nibbles with e8m0 block scales
+        (ops.quantize_expert_weights_mxfp4: one expert at a time), in place of the bf16 tensors,
+        which are freed.  A scale belongs to 32 input features of a stored row, so the gate|up
+        rows are quantised in their interleaved order."""
+        if self.is_mxfp4:
+            return
+        if self.is_fp8:
+            raise ValueError("quantize_experts_mxfp4: the experts are fp8 already")
+        for name in ("w_gate_up", "w_down"):
+            packed, scales = ops.quantize_expert_weights_mxfp4(getattr(self, name).data)
+            setattr(self, name, nn.Parameter(packed, requires_grad=False))
+            setattr(self, name + "_block_scale", scales)
+
     def _expert_bf16(self, name: str, e: int) -> torch.Tensor:
-        """Expert e's weight as bf16: the tensor itself, or the dequantised fp8 rows."""
+        """Expert e's weight as bf16: the tensor itself, or the dequantised fp8 / MXFP4 rows."""
         w = getattr(self, name)[e]
+        if self.is_mxfp4:
+            return ops.dequantize_mxfp4(w, getattr(self, name + "_block_scale")[e])
         if not self.is_fp8:
             return w
         return (w.float() * getattr(self, name + "_scale")[e][:, None]).to(torch.bfloat16)
@@ -336,7 +363,8 @@ class MoEMLP(nn.Module):
         if x_q is not None or norm is not None:
             raise RuntimeError("MoEMLP takes normalised bf16 rows (the layer's generic body)")
         return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
-                           self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale)
+                           self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale,
+                           self.w_gate_up_block_scale, self.w_down_block_scale)
 
     # ------------------------------------------------------------------ weights
     def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
@@ -348,6 +376,9 @@ class MoEMLP(nn.Module):
         if self.is_fp8:
             raise RuntimeError("MoEMLP.load_hf on fp8 experts: load the bf16 weights first, then "
                                "quantize_experts_fp8()")
+        if self.is_mxfp4:
+            raise RuntimeError("MoEMLP.load_hf on MXFP4 experts: load the bf16 weights first, "
+                               "then quantize_experts_mxfp4()")
         pre = next((p for p in ("mlp.", "block_sparse_moe.") if p + "gate.weight" in sd), None)
         if pre is None:
             g("block_sparse_moe.gate.weight" if self.mixtral_keys else "mlp.gate.weight")
@@ -371,7 +402,7 @@ class MoEMLP(nn.Module):
 
     def hf_dict(self) -> dict:
         """The hub's per-expert layout (inverse of :meth:`load_hf`); fp8 experts as their
-        dequantised weights rounded to bf16."""
+        dequantised weights rounded to bf16, MXFP4 experts as their dequantised weights (exact)."""
         pre, names = (("block_sparse_moe.", ("w1", "w3", "w2")) if self.mixtral_keys else
                       ("mlp.", ("gate_proj", "up_proj", "down_proj")))
         sd = {pre + "gate.weight": self.gate.weight}

@@ -24,7 +24,8 @@ def apply_quantization(block, mode, threshold: float = 6.0):
     """Quantise a Llama / GPT-2 block in place: ``mode`` False / None / "none" (bf16), True /
     "fp8" (e4m3 weights, per-channel scales), "int8" (LLM.int8, outlier ``threshold``) or
     "mxfp4" / "fp4" (OCP MX 4-bit e2m1 weights, one e8m0 scale per 32 input features), or
-    "fp8_experts" (sparse-MoE models: e4m3 expert weights with per-row scales, the rest bf16)."""
+    "fp8_experts" (sparse-MoE models: e4m3 expert weights with per-row scales, the rest bf16) or
+    "mxfp4_experts" (sparse-MoE models: MXFP4 expert weights, the rest bf16)."""
     if mode in (False, None, "none", "bf16"):
         return block
     if mode is True or mode == "fp8":
@@ -41,8 +42,13 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise ValueError(f"fp8_experts needs a sparse MoE model; {type(block).__name__} has "
                              "no experts")
         return block.quantize_experts_fp8()
+    if mode == "mxfp4_experts":
+        if not hasattr(block, "quantize_experts_mxfp4"):
+            raise ValueError(f"mxfp4_experts needs a sparse MoE model; {type(block).__name__} "
+                             "has no experts")
+        return block.quantize_experts_mxfp4()
     raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / "
-                     "fp8_experts)")
+                     "fp8_experts / mxfp4_experts)")
 
 
 def make_block(spec: ModelSpec, layer_ids, device=None, dtype=torch.bfloat16):
@@ -102,11 +108,16 @@ class CausalLMStage(nn.Module):
         apply_quantization(self.block, "fp8_experts")
         return self
 
+    def quantize_experts_mxfp4(self) -> "CausalLMStage":
+        apply_quantization(self.block, "mxfp4_experts")
+        return self
+
     def quantize(self, mode, threshold: float = 6.0) -> "CausalLMStage":
         """``mode``: False / None / "none"; True / "fp8" (e4m3, the MI355X default); "int8"
         (LLM.int8 with outlier ``threshold``); "mxfp4" / "fp4" (4-bit MX weights: the
         interactive-decode and capacity mode; the LM head and embeddings stay bf16);
-        "fp8_experts" (sparse-MoE models: only the routed experts' weights become e4m3)."""
+        "fp8_experts" / "mxfp4_experts" (sparse-MoE models: only the routed experts' weights
+        become e4m3 / MXFP4)."""
         apply_quantization(self.block, mode, threshold)
         return self
 

@@ -566,6 +566,22 @@ def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor,
     return o
 
 
+def quantize_expert_weights_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Offline MXFP4 quantisation of stacked expert weights ``[E, N, K]`` (K % 32 == 0):
+    :func:`quantize_weight_mxfp4` one expert at a time.  A block scale belongs to 32 k of a stored
+    row, so gate|up rows are quantised after :func:`swiglu_interleave`.  Returns ``(packed
+    [E, N, K / 2] uint8, scales [E, N, K / 32] uint8)``."""
+    if w.dim() != 3 or w.shape[2] % MXFP4_BLOCK or w.shape[2] == 0:
+        raise ValueError(f"quantize_expert_weights_mxfp4: [E, N, K] with K % {MXFP4_BLOCK} == 0, "
+                         f"got {tuple(w.shape)}")
+    E, N, K = w.shape
+    packed = torch.empty(E, N, K // 2, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(E, N, K // MXFP4_BLOCK, dtype=torch.uint8, device=w.device)
+    for e in range(E):
+        packed[e], scales[e] = quantize_weight_mxfp4(w[e])
+    return packed, scales
+
+
 def softmax_scale(head_dim: int) -> float:
     return 1.0 / math.sqrt(head_dim)
 
@@ -1394,7 +1410,8 @@ def moe_route(logits: torch.Tensor, k: int, renorm: bool) -> MoERouting:
 
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
-                     w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     w_scale: Optional[torch.Tensor] = None,
+                     w_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
     ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
     rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
@@ -1402,19 +1419,42 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     ``y [P, H]`` with row j of h at row ``sorted_pairs[j]`` (the pair index).  ``out`` may have
     more than P rows; the rest are not touched.  With ``w_scale [E, N]`` (fp32) ``w`` is fp8
     e4m3fn (:func:`quantize_expert_weights_fp8`): the row scale multiplies the fp32 product, the
-    activations stay bf16."""
+    activations stay bf16.  With ``w_block_scale [E, N, K / 32]`` (uint8 e8m0) ``w`` is MXFP4
+    nibbles ``uint8 [E, N, K / 2]`` (:func:`quantize_expert_weights_mxfp4`), widened exactly to
+    bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights."""
     T, k = r.topk_ids.shape
     P, N = T * k, w.shape[1]
+    if w_block_scale is not None or w.dtype == torch.uint8:
+        if w_scale is not None:
+            raise ValueError("moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both")
+        if w_block_scale is None:
+            raise ValueError("moe_grouped_gemm: uint8 (MXFP4) weights need w_block_scale "
+                             "[E, N, K / 32]")
+        if w.dtype != torch.uint8 or w.dim() != 3:
+            raise ValueError("moe_grouped_gemm: w_block_scale goes with uint8 MXFP4 weights "
+                             "[E, N, K / 2]")
+        if (w_block_scale.dtype != torch.uint8 or w_block_scale.device != w.device
+                or tuple(w_block_scale.shape) != (w.shape[0], N, w.shape[2] // 16)
+                or w.shape[2] % 16):
+            raise ValueError("moe_grouped_gemm: w_block_scale uint8 [E, N, K / 32] on the "
+                             "weights' device")
+        if w.shape[2] % 64:
+            raise ValueError("moe_grouped_gemm: needs K % 128 == 0")
     if out is None:
         out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=x.device)
     if not _gpu(x):
-        ok = (w.dtype == torch.bfloat16 if w_scale is None else
-              w.dtype == FP8 and tuple(w_scale.shape) == (w.shape[0], N))
+        ok = (w_block_scale is not None or
+              (w.dtype == torch.bfloat16 if w_scale is None else
+               w.dtype == FP8 and tuple(w_scale.shape) == (w.shape[0], N)))
         if not ok:
             raise ValueError("moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with "
                              "w_scale [E, N]")
-        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale)
-    if w_scale is None:
+        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale, w_block_scale)
+    if w_block_scale is not None:
+        native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
+                                  r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0,
+                                  None, w_block_scale.contiguous())
+    elif w_scale is None:
         native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
                                   r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0)
     else:
@@ -1440,12 +1480,17 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor,
 def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
             w_down: torch.Tensor, k: int, renorm: bool,
             w_gate_up_scale: Optional[torch.Tensor] = None,
-            w_down_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+            w_down_scale: Optional[torch.Tensor] = None,
+            w_gate_up_block_scale: Optional[torch.Tensor] = None,
+            w_down_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
     SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
     expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
-    with their row scales ``[E, 2I]`` / ``[E, H]``."""
+    with their row scales ``[E, 2I]`` / ``[E, H]``, or MXFP4 nibbles ``[E, 2I, H / 2]`` /
+    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``."""
     r = moe_route(gate_logits, k, renorm)
-    h = moe_grouped_gemm(x, w_gate_up, r, w_scale=w_gate_up_scale)
-    y = moe_grouped_gemm(h, w_down, r, down=True, w_scale=w_down_scale)
+    h = moe_grouped_gemm(x, w_gate_up, r, w_scale=w_gate_up_scale,
+                         w_block_scale=w_gate_up_block_scale)
+    y = moe_grouped_gemm(h, w_down, r, down=True, w_scale=w_down_scale,
+                         w_block_scale=w_down_block_scale)
     return moe_combine(y, r.topk_w)

@@ -442,11 +442,14 @@ def _swiglu_interleaved(gu: torch.Tensor) -> torch.Tensor:
 
 
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: int,
-                     out: torch.Tensor, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: torch.Tensor, w_scale: Optional[torch.Tensor] = None,
+                     w_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``epilogue`` 0: ``out[j] = swiglu(x[sorted_pairs[j] // k] . w[e]^T)`` for the rows j of
     expert e (``w [E, 2I, H]``, rows in ``ops.swiglu_interleave`` order); 1:
     ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding.
-    ``w_scale [E, N]``: ``w`` is fp8 and row n of expert e is ``w[e, n] * w_scale[e, n]``."""
+    ``w_scale [E, N]``: ``w`` is fp8 and row n of expert e is ``w[e, n] * w_scale[e, n]``.
+    ``w_block_scale [E, N, K / 32]``: ``w`` is MXFP4 nibbles ``[E, N, K / 2]`` and expert e is
+    ``dequantize_mxfp4(w[e], w_block_scale[e])``."""
     k = r.topk_ids.shape[1]
     off = r.expert_offset.tolist()
     pairs = r.sorted_pairs.long()
@@ -454,7 +457,10 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: 
         a, b = off[e], off[e + 1]
         if a == b:
             continue
-        wf = w[e].float()
+        if w_block_scale is not None:
+            wf = dequantize_mxfp4(w[e], w_block_scale[e]).float()
+        else:
+            wf = w[e].float()
         if w_scale is not None:
             wf = wf * w_scale[e].float()[:, None]
         wf = wf.t()

@@ -44,7 +44,8 @@ class EngineConfig:
     dtype: str = "bf16"
     quantize: object = False        # False | True / "fp8" (e4m3 weights) | "int8" (LLM.int8) |
                                     # "mxfp4" / "fp4" (4-bit MX weights) | "fp8_experts" (sparse
-                                    # MoE: e4m3 expert weights, the rest bf16)
+                                    # MoE: e4m3 expert weights, the rest bf16) | "mxfp4_experts"
+                                    # (sparse MoE: MXFP4 expert weights, the rest bf16)
     int8_threshold: float = 6.0     # LLM.int8 outlier threshold (quantize="int8")
     pp: int = 1
     dp: int = 1                     # pipeline replicas (world = dp x pp in init_pipeline_rank)

@@ -148,7 +148,7 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
                dtype: torch.dtype = torch.bfloat16, random_init: bool = False,
                seed: int = 0) -> LlamaBlock:
     """Build the block of ``layer_ids`` and load its weights (per layer, only the needed shards).
-    ``use_quantized``: False, True / "fp8", "int8", "mxfp4" or "fp8_experts"
+    ``use_quantized``: False, True / "fp8", "int8", "mxfp4", "fp8_experts" or "mxfp4_experts"
     (``apply_quantization``'s modes)."""
     spec = _load_config(model_name, cache_dir, token)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
@@ -176,6 +176,8 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
     per parameter; Llama-family blocks) — the interactive-decode and capacity mode.
     ``quantize="fp8_experts"``: sparse-MoE blocks only — the routed experts' weights as fp8 e4m3
     with one scale per weight row; attention, norms and the router stay bf16.
+    ``quantize="mxfp4_experts"``: the same with MXFP4 expert weights (one e8m0 scale per 32 input
+    features of a weight row).
     """
     if device is None:
         if not torch.cuda.is_available():

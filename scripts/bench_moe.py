@@ -5,6 +5,7 @@ scripts/bench_mxfp4.py's protocol and helpers.
 
     python3 scripts/bench_moe.py [--models qwen3-30b-a3b,mixtral-8x7b] [--rows 1,8,64,512] [--out DIR]
     python3 scripts/bench_moe.py --fp8 [...]      fp8 expert weights against bf16 -> moe_fp8.json
+    python3 scripts/bench_moe.py --fp4 [...]      MXFP4 and fp8 against bf16 -> moe_fp4.json
 
 Per model (one layer's shapes) and per decode row count T, with random router logits:
 
@@ -25,6 +26,12 @@ against bf16 instead: candidates ``moe`` / ``gate_up`` / ``down`` and ``moe_fp8`
 ``gate_up_fp8`` / ``down_fp8``, the same graphs over copies, interleaved in the same process.
 Reported per fp8 candidate: TB/s on the fp8 bytes (the hit experts' 3 H I bytes and their 2 I + H
 fp32 row scales) and the time ratio to its bf16 twin.  Results: ``<out>/moe_fp8.json``.
+
+``--fp4`` adds MXFP4 expert weights (ops.quantize_expert_weights_mxfp4 of the same bf16 tensors):
+candidates ``moe_fp4`` / ``gate_up_fp4`` / ``down_fp4`` next to the bf16 and fp8 ones, all nine
+interleaved in the same process.  Their TB/s is on 17/32 byte per hit expert weight (nibbles and
+block scales); ``vs_fp8`` is the time ratio to the fp8 twin and ``bytes_vs_fp8`` the byte ratio
+it is held against.  Results: ``<out>/moe_fp4.json``.
 """
 import argparse
 import os
@@ -47,17 +54,22 @@ def bench_model(torch, ops, F, name, rows, res, a):
     copies = 8 if layer_bytes < (2 << 30) else 3
     if a.fp8 and copies == 8:
         copies = 16                                   # ... at half the bytes per expert
+    if a.fp4:
+        copies = 32 if copies == 8 else 4             # ... at 17/64 of them
     gen = torch.Generator(device=dev).manual_seed(1)
     wgu = [torch.empty(E, 2 * I, H, device=dev, dtype=torch.bfloat16).normal_(0, H ** -0.5, generator=gen)
            for _ in range(copies)]
     wd = [torch.empty(E, H, I, device=dev, dtype=torch.bfloat16).normal_(0, I ** -0.5, generator=gen)
           for _ in range(copies)]
-    if a.fp8:
-        q = [(ops.quantize_expert_weights_fp8(wgu[c]), ops.quantize_expert_weights_fp8(wd[c]))
-             for c in range(copies)]
-        wgu8, sgu = [p[0][0] for p in q], [p[0][1] for p in q]
-        wd8, sd = [p[1][0] for p in q], [p[1][1] for p in q]
-        del q
+    # per quantised format: (gate|up weights, down weights, their scales, the scale keyword)
+    quant = {}
+    for fmt, on, fn, kw in (("fp8", a.fp8 or a.fp4, ops.quantize_expert_weights_fp8, "w_scale"),
+                            ("fp4", a.fp4, ops.quantize_expert_weights_mxfp4, "w_block_scale")):
+        if on:
+            q = [(fn(wgu[c]), fn(wd[c])) for c in range(copies)]
+            quant[fmt] = ([p[0][0] for p in q], [p[1][0] for p in q], [p[0][1] for p in q],
+                          [p[1][1] for p in q], kw)
+            del q
     for T in rows:
         x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
         logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
@@ -96,22 +108,28 @@ def bench_model(torch, ops, F, name, rows, res, a):
             "combine": lambda c: ops.moe_combine(ys[c], routes[c].topk_w),
         }
         cands = {"moe": moe, "loop": loop, **parts}
-        if a.fp8:
-            def moe_fp8(c):
-                return ops.moe_mlp(x, logits[c], wgu8[c], wd8[c], k, spec.norm_topk_prob,
-                                   sgu[c], sd[c])
+        errq = {}
+        if quant:
+            cands = {"moe": moe, "gate_up": parts["gate_up"], "down": parts["down"]}
+        for fmt, (qgu, qd, sgu, sd, kw) in quant.items():
+            def moe_q(c, qgu=qgu, qd=qd, sgu=sgu, sd=sd, kw=kw):
+                return ops.moe_mlp(x, logits[c], qgu[c], qd[c], k, spec.norm_topk_prob,
+                                   **{"w_gate_up_" + kw[2:]: sgu[c], "w_down_" + kw[2:]: sd[c]})
 
-            h8 = [ops.moe_grouped_gemm(x, wgu8[c], routes[c], w_scale=sgu[c]) for c in range(copies)]
-            y8 = [torch.empty_like(ys[c]) for c in range(copies)]
-            cands = {
-                "moe": moe, "gate_up": parts["gate_up"], "down": parts["down"],
-                "moe_fp8": moe_fp8,
-                "gate_up_fp8": lambda c: ops.moe_grouped_gemm(x, wgu8[c], routes[c], out=h8[c],
-                                                              w_scale=sgu[c]),
-                "down_fp8": lambda c: ops.moe_grouped_gemm(h8[c], wd8[c], routes[c], down=True,
-                                                           out=y8[c], w_scale=sd[c]),
-            }
-            err8 = (moe_fp8(0).float() - moe(0).float()).abs().max().item()
+            hq = [ops.moe_grouped_gemm(x, qgu[c], routes[c], **{kw: sgu[c]}) for c in range(copies)]
+            yq = [torch.empty_like(ys[c]) for c in range(copies)]
+            cands["moe_" + fmt] = moe_q
+
+            def gate_up_q(c, qgu=qgu, sgu=sgu, kw=kw, hq=hq):
+                return ops.moe_grouped_gemm(x, qgu[c], routes[c], out=hq[c], **{kw: sgu[c]})
+
+            def down_q(c, qd=qd, sd=sd, kw=kw, hq=hq, yq=yq):
+                return ops.moe_grouped_gemm(hq[c], qd[c], routes[c], down=True, out=yq[c],
+                                            **{kw: sd[c]})
+
+            cands["gate_up_" + fmt] = gate_up_q
+            cands["down_" + fmt] = down_q
+            errq[fmt] = (moe_q(0).float() - moe(0).float()).abs().max().item()
         graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
                   for n, f in cands.items()}
         samples = {n: [] for n in cands}
@@ -127,21 +145,32 @@ def bench_model(torch, ops, F, name, rows, res, a):
                       "max_us": round(max(samples[n]), 2)}
         res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
         res["models"][name]["rows"][str(T)] = row
-        if a.fp8:
+        if quant:
             # bytes of one layer's hit experts: gate|up is 2 / 3 of the weights and 2 I of the rows
             byt = {"moe": touched, "gate_up": touched * 2 / 3, "down": touched / 3}
             sc = {"moe": hit * (2 * I + H) * 4, "gate_up": hit * 2 * I * 4, "down": hit * H * 4}
-            row["max_abs_diff_fp8_vs_bf16"] = round(err8, 4)
+            for fmt in quant:
+                row[f"max_abs_diff_{fmt}_vs_bf16"] = round(errq[fmt], 4)
             for n in ("moe", "gate_up", "down"):
                 row[n]["expert_TBps"] = round(byt[n] / row[n]["us"] / 1e6, 3)
                 f8 = row[n + "_fp8"]
                 f8["expert_TBps"] = round((byt[n] / 2 + sc[n]) / f8["us"] / 1e6, 3)
                 f8["vs_bf16"] = round(f8["us"] / row[n]["us"], 3)
+                if a.fp4:   # 17/32 byte per weight: the nibbles and one scale byte per 32
+                    f4 = row[n + "_fp4"]
+                    f4["expert_TBps"] = round(byt[n] * 17 / 64 / f4["us"] / 1e6, 3)
+                    f4["vs_bf16"] = round(f4["us"] / row[n]["us"], 3)
+                    f4["vs_fp8"] = round(f4["us"] / f8["us"], 3)
+                    f4["bytes_vs_fp8"] = round(byt[n] * 17 / 64 / (byt[n] / 2 + sc[n]), 3)
+            last = "fp4" if a.fp4 else "fp8"
             print(f"{name:14s} T={T:4d} hit {hit:6.1f}  " + "  ".join(
-                f"{n} {row[n]['us']:.1f} / fp8 {row[n + '_fp8']['us']:.1f} us "
-                f"({row[n + '_fp8']['expert_TBps']:.2f} TB/s, x{row[n + '_fp8']['vs_bf16']:.3f})"
+                f"{n} " + " / ".join(f"{row[n + s]['us']:.1f}"
+                                     for s in [""] + ["_" + f for f in quant])
+                + f" us ({row[n + '_' + last]['expert_TBps']:.2f} TB/s, "
+                f"x{row[n + '_' + last]['vs_bf16']:.3f}"
+                + (f", x{row[n + '_fp4']['vs_fp8']:.3f} of fp8" if a.fp4 else "") + ")"
                 for n in ("moe", "gate_up", "down")), flush=True)
-            bm._save(a, "moe_fp8.json", res)
+            bm._save(a, "moe_fp4.json" if a.fp4 else "moe_fp8.json", res)
             del graphs
             torch.cuda.empty_cache()
             continue
@@ -164,7 +193,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(bm.REPO, "profiles", "moe"))
     ap.add_argument("--fp8", action="store_true",
                     help="fp8 expert weights against bf16 (moe_fp8.json) instead of moe against loop")
-    ap.add_argument("--note", default="", help="free text kept in the result file (--fp8)")
+    ap.add_argument("--fp4", action="store_true",
+                    help="MXFP4 and fp8 expert weights against bf16 (moe_fp4.json)")
+    ap.add_argument("--note", default="", help="free text kept in the result file (--fp8 / --fp4)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
@@ -177,7 +208,7 @@ def main():
                                   "index_add_ (fp32); routing on the host, not timed",
                           "route / gate_up / down / combine": "moe's launches, each alone"},
            "models": {}}
-    if a.fp8:
+    if a.fp8 or a.fp4:
         res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
                        "`copies` layers); expert_TBps = the hit experts' weight bytes in the "
                        "candidate's format (fp8: plus their fp32 row scales) / time; vs_bf16 = "
@@ -186,8 +217,16 @@ def main():
                                                      "two grouped GEMMs alone)",
                              "moe_fp8 / gate_up_fp8 / down_fp8": "the same on "
                              "ops.quantize_expert_weights_fp8 of the same tensors"}
-        if a.note:
-            res["note"] = a.note
+    if a.fp4:
+        res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
+                       "`copies` layers); expert_TBps = the hit experts' weight bytes in the "
+                       "candidate's format (fp8: plus their fp32 row scales; fp4: 17/32 byte per "
+                       "weight, nibbles and e8m0 block scales) / time; vs_bf16 / vs_fp8 = time / "
+                       "the bf16 / fp8 twin's time; bytes_vs_fp8 = the byte ratio to the fp8 twin")
+        res["candidates"]["moe_fp4 / gate_up_fp4 / down_fp4"] = (
+            "the same on ops.quantize_expert_weights_mxfp4 of the same tensors")
+    if (a.fp8 or a.fp4) and a.note:
+        res["note"] = a.note
     with torch.no_grad():
         for name in a.models.split(","):
             bench_model(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")], res, a)
