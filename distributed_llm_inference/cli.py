@@ -42,7 +42,7 @@ def _common(ap: argparse.ArgumentParser) -> None:
                          "parameter; the interactive-decode and KV-capacity mode)")
     wq.add_argument("--fp8-experts", action="store_true",
                     help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
-                         "attention, norms and the router stay bf16")
+                         "attention, norms, the router, dense layers and a shared expert stay bf16")
     wq.add_argument("--fp4-experts", action="store_true",
                     help="sparse-MoE models: MXFP4 expert weights (4-bit e2m1 + e8m0 scale per 32: "
                          "17/32 byte per expert parameter); attention, norms and the router stay "
@@ -135,12 +135,21 @@ def cmd_plan(a) -> int:
         per_layer = experts + 2 * (spec.layer_param_count() - spec.expert_param_count())
         per_param = per_layer / spec.layer_param_count()
     emb = spec.vocab_size * spec.hidden_size * 2
+
+    def layer_bytes(i: int) -> int:
+        """Layer i's weight bytes: per_layer for a sparse layer (every layer of the models
+        without a layer pattern); a dense layer of a mixed stack has no routed experts, so the
+        expert-only modes leave all of it bf16 (as they leave the shared expert)."""
+        if not spec.num_experts or spec.is_sparse_layer(i):
+            return per_layer
+        expert_mode = getattr(a, "fp8_experts", False) or getattr(a, "fp4_experts", False)
+        return int(spec.layer_param_count(i) * (2 if expert_mode else per_param))
     replicas = []
     for r in range(layout.dp):
         out = []
         for i, (s, e) in enumerate(ranges):
             # every rank holds the LM head when it rotates (runtime/head.py)
-            w = (e - s) * per_layer + (emb if i == 0 else 0) + (
+            w = sum(layer_bytes(j) for j in range(s, e)) + (emb if i == 0 else 0) + (
                 emb if (i == len(ranges) - 1 or rotate) else 0)
             free = 288e9 * a.gpu_mem - w
             kv_tok = KVPool.bytes_per_block(spec, e - s, 1, 1 if a.kv_dtype == "fp8" else 2)

@@ -51,8 +51,8 @@ class ModelSpec:
     attention_bias: bool = False
     mlp_bias: bool = False
     name: str = "custom"
-    # Llama-family variants: "llama" | "mistral" | "qwen2" | "qwen3" | "qwen3_moe" | "mixtral"
-    # (the HF model_type)
+    # Llama-family variants: "llama" | "mistral" | "qwen2" | "qwen3" | "qwen3_moe" | "mixtral" |
+    # "qwen2_moe" (the HF model_type)
     model_type: str = "llama"
     # bias on o_proj; None = same as attention_bias (Llama).  Qwen2 has q/k/v bias only.
     o_proj_bias: Optional[bool] = None
@@ -64,17 +64,42 @@ class ModelSpec:
     # Qwen3: every q and k head is RMS-normalised over head_dim (learned weights q_norm / k_norm)
     # between the projection and RoPE
     qk_norm: bool = False
-    # sparse mixture-of-experts MLP in every layer ("qwen3_moe", "mixtral"): num_experts routed
+    # sparse mixture-of-experts MLP ("qwen3_moe", "mixtral", "qwen2_moe"): num_experts routed
     # experts of width moe_intermediate_size, num_experts_per_tok of them per token, the top-k
     # router weights optionally renormalised by their sum.  num_experts == 0: dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 0
     moe_intermediate_size: int = 0
     norm_topk_prob: bool = False
+    # "qwen2_moe": every token of a sparse layer also goes through one dense SwiGLU expert of this
+    # width, scaled by sigmoid(shared_expert_gate(x)) (a Linear H -> 1).  0: no shared expert
+    shared_expert_intermediate_size: int = 0
+    # "qwen2_moe": layer i is sparse when i is not in mlp_only_layers and (i + 1) %
+    # decoder_sparse_step == 0 (is_sparse_layer); every other layer is a dense MLP of width
+    # intermediate_size
+    decoder_sparse_step: int = 1
+    mlp_only_layers: Tuple[int, ...] = ()
 
     def __post_init__(self):
         if self.num_experts == 0:
+            if self.shared_expert_intermediate_size:
+                raise ValueError("shared_expert_intermediate_size needs a sparse MoE model "
+                                 "(num_experts > 0)")
             return
+        object.__setattr__(self, "mlp_only_layers",
+                           tuple(sorted({int(i) for i in self.mlp_only_layers})))
+        s = self.shared_expert_intermediate_size
+        if s < 0 or s % 128:
+            raise ValueError(f"shared_expert_intermediate_size={s}: a positive multiple of 128 "
+                             "(or 0: no shared expert)")
+        if any(not 0 <= i < self.num_layers for i in self.mlp_only_layers):
+            raise ValueError(f"mlp_only_layers={list(self.mlp_only_layers)}: entries must lie in "
+                             f"[0, {self.num_layers})")
+        if self.decoder_sparse_step < 1 or not any(
+                self.is_sparse_layer(i) for i in range(self.num_layers)):
+            raise ValueError(f"decoder_sparse_step={self.decoder_sparse_step}, mlp_only_layers="
+                             f"{list(self.mlp_only_layers)} leave no sparse layer among "
+                             f"{self.num_layers}: describe the model as a dense one")
         e, k, h, i = (self.num_experts, self.num_experts_per_tok, self.hidden_size,
                       self.moe_intermediate_size)
         if self.arch != "llama" or e < 0:
@@ -120,24 +145,46 @@ class ModelSpec:
     def rope_scaling_dict(self) -> Optional[Dict[str, Any]]:
         return dict(self.rope_scaling) if self.rope_scaling is not None else None
 
-    def layer_param_count(self) -> int:
+    def is_sparse_layer(self, i: int) -> bool:
+        """Whether layer ``i`` carries the sparse MoE MLP (HF ``Qwen2MoeDecoderLayer``'s rule);
+        False for every layer of a model without experts."""
+        return (self.num_experts > 0 and i not in self.mlp_only_layers
+                and (i + 1) % self.decoder_sparse_step == 0)
+
+    def layer_param_count(self, layer_idx: Optional[int] = None) -> int:
+        """Parameters of layer ``layer_idx``; without an index, of a sparse layer for a model
+        with experts (every layer of an all-sparse stack), else of the model's one layer kind."""
         h, i = self.hidden_size, self.intermediate_size
         if self.arch == "gpt2":
             return 4 * h * h + 4 * h + 2 * h * i + i + h + 4 * h
         qk = 2 * self.head_dim if self.qk_norm else 0
+        bias = 0
+        if self.num_experts:   # models with experts count exactly (Qwen2-MoE's q/k/v bias); the
+            # dense models' figure, which leaves the bias vectors out, is kept as it was
+            bias = (self.qkv_size if self.attention_bias else 0) + (
+                h if self.has_o_proj_bias else 0)
         mlp = 3 * h * i
-        if self.num_experts:   # the router + every expert's gate, up and down
-            mlp = h * self.num_experts + self.num_experts * 3 * h * self.moe_intermediate_size
-        return h * self.qkv_size + self.q_size * h + mlp + 2 * h + qk
+        sparse = self.num_experts > 0 if layer_idx is None else self.is_sparse_layer(layer_idx)
+        if sparse:   # the router + every expert's gate, up and down (+ the shared expert, its gate)
+            mlp = h * self.num_experts + self.expert_param_count()
+            if self.shared_expert_intermediate_size:
+                mlp += 3 * h * self.shared_expert_intermediate_size + h
+        return h * self.qkv_size + self.q_size * h + mlp + 2 * h + qk + bias
 
-    def expert_param_count(self) -> int:
-        """Per layer: every routed expert's gate, up and down (0 for a dense model)."""
+    def expert_param_count(self, layer_idx: Optional[int] = None) -> int:
+        """Per layer: every routed expert's gate, up and down (0 for a dense model and for a
+        dense layer of a mixed stack)."""
+        if layer_idx is not None and not self.is_sparse_layer(layer_idx):
+            return 0
         return self.num_experts * 3 * self.hidden_size * self.moe_intermediate_size
 
     def param_count(self) -> int:
         emb = self.vocab_size * self.hidden_size
         head = 0 if self.tie_word_embeddings else emb
-        return self.num_layers * self.layer_param_count() + emb + head + self.hidden_size
+        if self.arch == "gpt2":
+            return self.num_layers * self.layer_param_count() + emb + head + self.hidden_size
+        layers = sum(self.layer_param_count(i) for i in range(self.num_layers))
+        return layers + emb + head + self.hidden_size
 
     def kv_bytes_per_token_per_layer(self, dtype_bytes: int = 2) -> int:
         return 2 * self.num_kv_heads * self.head_dim * dtype_bytes
@@ -187,19 +234,22 @@ class ModelSpec:
                 mlp_bias=True,
                 name=cfg.get("_name_or_path", "gpt2") or "gpt2",
             )
-        if mt not in ("llama", "mistral", "qwen2", "qwen3", "qwen3_moe", "mixtral"):
+        if mt not in ("llama", "mistral", "qwen2", "qwen3", "qwen3_moe", "mixtral", "qwen2_moe"):
             raise ValueError(f"unsupported model_type {mt!r} (supported: llama, mistral, qwen2, "
-                             "qwen3, qwen3_moe, mixtral, gpt2)")
+                             "qwen3, qwen3_moe, mixtral, qwen2_moe, gpt2)")
         # Qwen2: q/k/v projections always carry a bias, o_proj never does (no config key)
-        qwen2 = mt == "qwen2"
+        # (Qwen2-MoE: the same attention)
+        qwen2 = mt in ("qwen2", "qwen2_moe")
         # Qwen3: per-head q/k RMSNorm; attention_bias from the config, for q/k/v and o_proj alike
         # (Qwen3-MoE: the same attention)
         qwen3 = mt in ("qwen3", "qwen3_moe")
         moe: Dict[str, Any] = {}
-        if mt == "qwen3_moe" and cfg.get("num_experts") is None:
+        if mt in ("qwen3_moe", "qwen2_moe") and cfg.get("num_experts") is None:
             # transformers 5.x serialises Qwen3MoeConfig.num_experts under Mixtral's name
             cfg = dict(cfg, num_experts=cfg.get("num_local_experts"))
         need = {"qwen3_moe": ("num_experts", "num_experts_per_tok", "moe_intermediate_size"),
+                "qwen2_moe": ("num_experts", "num_experts_per_tok", "moe_intermediate_size",
+                              "shared_expert_intermediate_size"),
                 "mixtral": ("num_local_experts", "num_experts_per_tok", "intermediate_size")}
         lacking = [k for k in need.get(mt, ()) if cfg.get(k) is None]
         if lacking:
@@ -215,6 +265,20 @@ class ModelSpec:
                        num_experts_per_tok=cfg["num_experts_per_tok"],
                        moe_intermediate_size=cfg["moe_intermediate_size"],
                        norm_topk_prob=bool(cfg.get("norm_topk_prob", False)))
+        elif mt == "qwen2_moe":
+            # a shared expert in every sparse layer, and HF's rule for which layers are sparse
+            # (ModelSpec.is_sparse_layer); the spec's own checks refuse what is not supported
+            moe = dict(num_experts=cfg["num_experts"],
+                       num_experts_per_tok=cfg["num_experts_per_tok"],
+                       moe_intermediate_size=cfg["moe_intermediate_size"],
+                       norm_topk_prob=bool(cfg.get("norm_topk_prob", False)),
+                       shared_expert_intermediate_size=cfg["shared_expert_intermediate_size"],
+                       decoder_sparse_step=int(cfg.get("decoder_sparse_step", 1) or 1),
+                       mlp_only_layers=tuple(cfg.get("mlp_only_layers") or ()))
+            if moe["shared_expert_intermediate_size"] <= 0:
+                raise ValueError("qwen2_moe: shared_expert_intermediate_size="
+                                 f"{moe['shared_expert_intermediate_size']}: a positive multiple "
+                                 "of 128 is supported")
         elif mt == "mixtral":
             # the expert width is intermediate_size; the top-k weights are always renormalised
             moe = dict(num_experts=cfg["num_local_experts"],
@@ -265,7 +329,9 @@ class ModelSpec:
             eos_token_id=eos,
             hidden_act=cfg.get("hidden_act", "silu"),
             pretraining_tp=cfg.get("pretraining_tp", 1) or 1,
-            attention_bias=True if qwen2 else bool(cfg.get("attention_bias", False)),
+            # (Qwen2-MoE spells its q/k/v bias switch qkv_bias; on unless the config says otherwise)
+            attention_bias=(bool(cfg.get("qkv_bias", True)) if mt == "qwen2_moe" else
+                            True if qwen2 else bool(cfg.get("attention_bias", False))),
             mlp_bias=bool(cfg.get("mlp_bias", False)),
             name=cfg.get("_name_or_path", mt) or mt,
             model_type=mt,
@@ -288,7 +354,7 @@ class ModelSpec:
             )
         arch_name = {"llama": "LlamaForCausalLM", "mistral": "MistralForCausalLM",
                      "qwen2": "Qwen2ForCausalLM", "qwen3": "Qwen3ForCausalLM",
-                     "qwen3_moe": "Qwen3MoeForCausalLM",
+                     "qwen3_moe": "Qwen3MoeForCausalLM", "qwen2_moe": "Qwen2MoeForCausalLM",
                      "mixtral": "MixtralForCausalLM"}[self.model_type]
         extra: Dict[str, Any] = {}
         if self.model_type in ("mistral", "mixtral"):
@@ -302,7 +368,15 @@ class ModelSpec:
                          moe_intermediate_size=self.moe_intermediate_size,
                          norm_topk_prob=self.norm_topk_prob, decoder_sparse_step=1,
                          mlp_only_layers=[])
-        if self.model_type in ("qwen2", "qwen3", "qwen3_moe"):
+        if self.model_type == "qwen2_moe":
+            extra.update(num_experts=self.num_experts,
+                         num_experts_per_tok=self.num_experts_per_tok,
+                         moe_intermediate_size=self.moe_intermediate_size,
+                         shared_expert_intermediate_size=self.shared_expert_intermediate_size,
+                         norm_topk_prob=self.norm_topk_prob, qkv_bias=self.attention_bias,
+                         decoder_sparse_step=self.decoder_sparse_step,
+                         mlp_only_layers=list(self.mlp_only_layers))
+        if self.model_type in ("qwen2", "qwen3", "qwen3_moe", "qwen2_moe"):
             extra.update(use_sliding_window=self.sliding_window is not None,
                          sliding_window=self.sliding_window)
         if self.model_type in ("qwen3", "qwen3_moe") and self.sliding_window is not None:
@@ -388,6 +462,22 @@ PRESETS: Dict[str, ModelSpec] = {
         rms_norm_eps=1e-5, rope_theta=1000000.0, max_position_embeddings=32768, bos_token_id=1,
         eos_token_id=2, num_experts=8, num_experts_per_tok=2, moe_intermediate_size=14336,
         norm_topk_prob=True),
+    # Qwen2-MoE: Qwen2 attention, a shared expert beside the routed ones in every sparse layer
+    # (shapes, like the presets above; both published models make every layer sparse)
+    "qwen1.5-moe-a2.7b": ModelSpec(
+        name="qwen1.5-moe-a2.7b", model_type="qwen2_moe", vocab_size=151936, hidden_size=2048,
+        intermediate_size=5632, num_layers=24, num_heads=16, num_kv_heads=16, head_dim=128,
+        rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=8192,
+        bos_token_id=151643, eos_token_id=151643, attention_bias=True, o_proj_bias=False,
+        num_experts=60, num_experts_per_tok=4, moe_intermediate_size=1408,
+        shared_expert_intermediate_size=5632, norm_topk_prob=False),
+    "qwen2-57b-a14b": ModelSpec(
+        name="qwen2-57b-a14b", model_type="qwen2_moe", vocab_size=151936, hidden_size=3584,
+        intermediate_size=18944, num_layers=28, num_heads=28, num_kv_heads=4, head_dim=128,
+        rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=32768,
+        bos_token_id=151643, eos_token_id=151643, attention_bias=True, o_proj_bias=False,
+        num_experts=64, num_experts_per_tok=8, moe_intermediate_size=2560,
+        shared_expert_intermediate_size=20480, norm_topk_prob=False),
     # tiny configs for CPU tests / smoke
     "tiny-llama": ModelSpec(
         name="tiny-llama", vocab_size=512, hidden_size=128, intermediate_size=256, num_layers=4,
@@ -456,6 +546,11 @@ def plan_stages(spec: ModelSpec, num_stages: int,
     during rebalancing); the default is uniform hardware.  ``head_rotation``: the decode steps'
     LM head runs on every rank in turn (runtime/head.py), so its cost is shared evenly instead of
     trimming the last stage.
+
+    Stages are balanced by layer count, also for a stack that mixes dense and sparse-MoE layers
+    (``ModelSpec.is_sparse_layer``): a sparse layer's decode cost follows the experts it hits,
+    not the bytes it holds, and nobody has measured the two layer kinds against each other, so
+    no weighting is guessed here.
     """
     L = spec.num_layers
     if num_stages < 1:

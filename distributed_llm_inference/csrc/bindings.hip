@@ -1000,17 +1000,35 @@ void small_gemm_fp8(Tensor out, Tensor x, Tensor w, Tensor wscale, optional<Tens
 }
 
 // ------------------------------------------------------------------------------ sparse MoE (moe.hip)
-void moe_topk(Tensor ids, Tensor w, Tensor logits, bool renorm) {
+// num_experts (with shared_w): logits [T, ld], ld > num_experts, column num_experts the shared
+// expert's gate logit; shared_w [T] gets its sigmoid
+void moe_topk(Tensor ids, Tensor w, Tensor logits, bool renorm, optional<int64_t> num_experts,
+              optional<Tensor> shared_w) {
   CHECK_IN(ids); CHECK_IN(w); CHECK_IN(logits);
   CHECK_I32(ids); CHECK_F32(w); CHECK_BF16(logits);
   TORCH_CHECK(logits.dim() == 2 && ids.dim() == 2 && w.dim() == 2, "moe_topk: 2-D tensors");
-  const int64_t T = logits.size(0), E = logits.size(1), k = ids.size(1);
+  TORCH_CHECK(num_experts.has_value() == shared_w.has_value(),
+              "moe_topk: num_experts and shared_w go together");
+  const int64_t T = logits.size(0), ld = logits.size(1), k = ids.size(1);
+  const int64_t E = num_experts.has_value() ? *num_experts : ld;
   TORCH_CHECK(T >= 1 && T <= (1 << 24), "moe_topk: 1 <= T <= 2^24");
   TORCH_CHECK(E >= 1 && E <= 256 && k >= 1 && k <= 8 && k <= E, "moe_topk: E <= 256, k <= min(8, E)");
   TORCH_CHECK(ids.size(0) == T && w.size(0) == T && w.size(1) == k, "moe_topk: ids / w [T, k]");
   TORCH_CHECK(ids.device() == logits.device() && w.device() == logits.device(),
               "moe_topk: one device");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  if (shared_w.has_value()) {
+    CHECK_IN(*shared_w); CHECK_F32(*shared_w);
+    TORCH_CHECK(E < ld && ld <= 65536,
+                "moe_topk: num_experts < logits.size(1) (the gate logit is column num_experts)");
+    TORCH_CHECK(shared_w->dim() == 1 && shared_w->size(0) == T &&
+                    shared_w->device() == logits.device(),
+                "moe_topk: shared_w fp32 [T] on the logits' device");
+    check_rc(dli::launch_moe_topk_shared(ids.data_ptr<int>(), w.data_ptr<float>(),
+                                         shared_w->data_ptr<float>(), bp(logits), (int)T, (int)E,
+                                         (int)ld, (int)k, renorm, cur_stream()), "moe_topk");
+    return;
+  }
   check_rc(dli::launch_moe_topk(ids.data_ptr<int>(), w.data_ptr<float>(), bp(logits), (int)T,
                                 (int)E, (int)k, renorm, cur_stream()), "moe_topk");
 }
@@ -1133,7 +1151,9 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
                                         (int)epilogue, cur_stream()), "moe_grouped_gemm");
 }
 
-void moe_combine(Tensor out, Tensor y, Tensor w) {
+// shared [T, H] (bf16) with shared_w [T] (fp32): the shared expert's term, added after the slots
+void moe_combine(Tensor out, Tensor y, Tensor w, optional<Tensor> shared,
+                 optional<Tensor> shared_w) {
   CHECK_IN(out); CHECK_IN(y); CHECK_IN(w);
   CHECK_BF16(out); CHECK_BF16(y); CHECK_F32(w);
   TORCH_CHECK(out.dim() == 2 && y.dim() == 2 && w.dim() == 2, "moe_combine: 2-D tensors");
@@ -1143,7 +1163,23 @@ void moe_combine(Tensor out, Tensor y, Tensor w) {
   TORCH_CHECK(w.size(0) == T && y.size(0) >= T * k && y.size(1) == H,
               "moe_combine: w [T, k], y [>= T k, H]");
   TORCH_CHECK(y.device() == out.device() && w.device() == out.device(), "moe_combine: one device");
+  TORCH_CHECK(shared.has_value() == shared_w.has_value(),
+              "moe_combine: shared and shared_w go together");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(out.device());
+  if (shared.has_value()) {
+    CHECK_IN(*shared); CHECK_IN(*shared_w);
+    TORCH_CHECK(shared->scalar_type() == at::kBFloat16 && shared->dim() == 2 &&
+                    shared->size(0) == T && shared->size(1) == H &&
+                    shared->device() == out.device(),
+                "moe_combine: shared bf16 [T, H], contiguous, on the output's device");
+    TORCH_CHECK(shared_w->scalar_type() == at::kFloat && shared_w->dim() == 1 &&
+                    shared_w->size(0) == T && shared_w->device() == out.device(),
+                "moe_combine: shared_w fp32 [T] on the output's device");
+    check_rc(dli::launch_moe_combine_shared(bp(out), bp(y), w.data_ptr<float>(), bp(*shared),
+                                            shared_w->data_ptr<float>(), (int)T, (int)k, (int)H,
+                                            cur_stream()), "moe_combine");
+    return;
+  }
   check_rc(dli::launch_moe_combine(bp(out), bp(y), w.data_ptr<float>(), (int)T, (int)k, (int)H,
                                    cur_stream()), "moe_combine");
 }
@@ -1393,7 +1429,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("w_scale"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("moe_topk", &moe_topk, "router logits [T, E] -> top-k expert ids + bf16-rounded weights",
-        py::arg("ids"), py::arg("w"), py::arg("logits"), py::arg("renorm"));
+        py::arg("ids"), py::arg("w"), py::arg("logits"), py::arg("renorm"),
+        py::arg("num_experts") = py::none(), py::arg("shared_w") = py::none());
   m.def("moe_group", &moe_group,
         "top-k ids [T, k] -> per-expert counts / offsets, stably sorted pairs and <= 32-row tiles",
         py::arg("ids"), py::arg("expert_count"), py::arg("expert_offset"),
@@ -1406,7 +1443,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none(),
         py::arg("w_block_scale") = py::none());
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
-        py::arg("out"), py::arg("y"), py::arg("w"));
+        py::arg("out"), py::arg("y"), py::arg("w"), py::arg("shared") = py::none(),
+        py::arg("shared_w") = py::none());
   m.def("dequant_mxfp4", &dequant_mxfp4, "bf16 [N, K] = MXFP4 nibbles [N, K / 2] * 2^(e8m0 - 127)",
         py::arg("out"), py::arg("w"), py::arg("block_scale"));
   m.def("quant_mx", &quant_mx, "MX fp8 quantiser: bf16 [M, K] -> e4m3 bytes + e8m0 per (row, 128)",

@@ -176,6 +176,11 @@ int moe_tile_capacity(int T, int E, int k);
 // (fp32 softmax probabilities, renorm: divided by their top-k sum; rounded to bf16)
 int launch_moe_topk(int* ids, float* w, const bf16* logits, int T, int E, int k, bool renorm,
                     hipStream_t stream);
+// the same on logits [T, ld], ld > E, whose column E is the shared expert's gate logit (columns
+// past E are padding, never read): ids / w as for the [:, :E] slice, and shared_w [T] =
+// sigmoid(logits[t, E]) rounded to bf16, held as fp32
+int launch_moe_topk_shared(int* ids, float* w, float* shared_w, const bf16* logits, int T, int E,
+                           int ld, int k, bool renorm, hipStream_t stream);
 // ids [P] -> expert_count [E], expert_offset [E + 1], sorted_pairs [P] (stable sort of the pair
 // index by expert), tiles of <= 32 rows (tile_expert / tile_start / tile_rows [cap]), n_tiles [1]
 int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int* sorted_pairs,
@@ -206,6 +211,10 @@ int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, con
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);
+// out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot] + shared_w[t] * shared[t]): fp32, the
+// slots in order, then the shared expert's term (shared [T, H] bf16, shared_w [T] fp32)
+int launch_moe_combine_shared(bf16* out, const bf16* y, const float* w, const bf16* shared,
+                              const float* shared_w, int T, int k, int H, hipStream_t stream);
 // MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip):
 // C[M, N] = (e4m3(a_q) * 2^(a_mx - 127)) . (e2m1(W) * 2^(bscale - 127))^T, fp32 accumulation.
 // a_q [M, K] bytes, a_mx in mx_off layout (launch_quant_mx), W / bscale as above; N % 256 == 0,

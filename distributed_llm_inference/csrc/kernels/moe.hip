@@ -1,4 +1,4 @@
-// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral) with bf16, fp8 (e4m3fn, one fp32 scale per
+// Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral, Qwen2-MoE) with bf16, fp8 (e4m3fn, one fp32 scale per
 // weight row) or MXFP4 (e2m1 nibbles, one e8m0 scale per 32 k) expert weights: routing, a grouped
 // weight-streaming MFMA GEMM over the hit experts, and the weighted combine.  Every grid is fixed
 // by (T, E, k, N) alone and every count is read from device memory, so the launches are
@@ -58,6 +58,20 @@
 //     scale is spent in the widening: nothing is left for the epilogue, and the activations are
 //     never quantised.
 //   * moe_combine.  out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order.
+//
+// Shared expert (Qwen2-MoE): every token of a sparse layer also runs one dense SwiGLU expert, on
+// the dense kernels, whose output s[t] is scaled by sigmoid(shared_expert_gate(x[t])).  The gate
+// row is stored behind the E router rows, so the router product hands over logits [T, ld] with
+// ld > E: columns 0 .. E - 1 are the router's, column E is the gate's logit, columns past E are
+// row padding and are never read.  Two template instantiations, kShared = true, carry it; the
+// kShared = false ones are the kernels above, unchanged:
+//   * moe_topk<true>: the row stride is ld; lane 0 also loads logits[t, E] and stores
+//     shared_w[t] = float(bf16(1 / (1 + exp(-logit)))) -- F.sigmoid of the bf16 logit, rounded
+//     to bf16 and held as fp32 like the top-k weights.  The column takes no part in the ranking
+//     or in the softmax sum: ids and w are those of the contiguous [:, :E] slice, bit for bit.
+//   * moe_combine<true>: out[t] = bf16(sum_slot w[t, slot] * y[t k + slot] + shared_w[t] * s[t]),
+//     fp32, the slots in order, then the shared term, then the one rounding; the vector width,
+//     the guard and the launch shape are moe_combine<false>'s.
 #include "kernels.h"
 
 namespace dli {
@@ -76,12 +90,21 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return v;
 }
 
+// kShared: logits rows are ld >= E + 1 apart and column E is the shared expert's gate logit
+// (shared_w [T] gets its sigmoid); else ld == E and shared_w is not touched
+template <bool kShared>
 __global__ void __launch_bounds__(kTopkWaves * 64)
 moe_topk_kernel(const bf16* __restrict__ logits, int* __restrict__ ids, float* __restrict__ w,
-                int T, int E, int k, int renorm) {
+                float* __restrict__ shared_w, int T, int E, int ld, int k, int renorm) {
   const int t = blockIdx.x * kTopkWaves + wave_id();
   if (t >= T) return;
   const int lane = lane_id();
+  if constexpr (kShared) {
+    if (lane == 0) {
+      const float gl = (float)logits[(size_t)t * ld + E];
+      shared_w[t] = (float)(bf16)(1.f / (1.f + expf(-gl)));
+    }
+  }
   // lane holds experts lane + 64 q; key = (ordered 16-bit logit + 1) << 8 | (255 - index), 0 =
   // absent or already taken
   unsigned key[4];
@@ -90,7 +113,7 @@ moe_topk_kernel(const bf16* __restrict__ logits, int* __restrict__ ids, float* _
   for (int q = 0; q < 4; ++q) {
     const int j = lane + 64 * q;
     unsigned bits = 0;
-    if (j < E) bits = __builtin_bit_cast(unsigned short, logits[(size_t)t * E + j]);
+    if (j < E) bits = __builtin_bit_cast(unsigned short, logits[(size_t)t * ld + j]);
     if (bits == 0x8000u) bits = 0;   // -0 ranks as +0
     const unsigned sk = (bits & 0x8000u) ? (~bits & 0xffffu) : (bits | 0x8000u);
     key[q] = j < E ? ((sk + 1) << 8) | (unsigned)(255 - j) : 0u;
@@ -488,8 +511,11 @@ moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
 }
 
 // ------------------------------------------------------------------------------------- combine
+// kShared: shared [T, H] (bf16) times shared_w [T] is added after the k slots
+template <bool kShared>
 __global__ void __launch_bounds__(256)
 moe_combine_kernel(const bf16* __restrict__ y, const float* __restrict__ w,
+                   const bf16* __restrict__ shared, const float* __restrict__ shared_w,
                    bf16* __restrict__ out, int T, int k, int H) {
   const int hv = H >> 3;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -502,6 +528,12 @@ moe_combine_kernel(const bf16* __restrict__ y, const float* __restrict__ w,
   for (int s = 0; s < k; ++s) {
     const float ws = w[t * k + s];
     const bf16x8 v = *reinterpret_cast<const bf16x8*>(y + (t * k + s) * H + c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += ws * (float)v[j];
+  }
+  if constexpr (kShared) {
+    const float ws = shared_w[t];
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(shared + t * H + c);
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] += ws * (float)v[j];
   }
@@ -522,8 +554,18 @@ int launch_moe_topk(int* ids, float* w, const bf16* logits, int T, int E, int k,
                     hipStream_t stream) {
   if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK || k > E) return -1;
   if (ids == nullptr || w == nullptr || logits == nullptr) return -5;
-  moe_topk_kernel<<<(T + kTopkWaves - 1) / kTopkWaves, kTopkWaves * 64, 0, stream>>>(
-      logits, ids, w, T, E, k, renorm ? 1 : 0);
+  moe_topk_kernel<false><<<(T + kTopkWaves - 1) / kTopkWaves, kTopkWaves * 64, 0, stream>>>(
+      logits, ids, w, nullptr, T, E, E, k, renorm ? 1 : 0);
+  return 0;
+}
+
+int launch_moe_topk_shared(int* ids, float* w, float* shared_w, const bf16* logits, int T, int E,
+                           int ld, int k, bool renorm, hipStream_t stream) {
+  if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK || k > E) return -1;
+  if (ld <= E || ld > (1 << 16)) return -2;   // column E must exist in every row
+  if (ids == nullptr || w == nullptr || logits == nullptr || shared_w == nullptr) return -5;
+  moe_topk_kernel<true><<<(T + kTopkWaves - 1) / kTopkWaves, kTopkWaves * 64, 0, stream>>>(
+      logits, ids, w, shared_w, T, E, ld, k, renorm ? 1 : 0);
   return 0;
 }
 
@@ -597,7 +639,20 @@ int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, i
                        hipStream_t stream) {
   if (T <= 0 || k <= 0 || k > kMaxTopK || H <= 0 || H % 8 != 0) return -1;
   const size_t n = (size_t)T * (H / 8);
-  moe_combine_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(y, w, out, T, k, H);
+  moe_combine_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(
+      y, w, nullptr, nullptr, out, T, k, H);
+  return 0;
+}
+
+int launch_moe_combine_shared(bf16* out, const bf16* y, const float* w, const bf16* shared,
+                              const float* shared_w, int T, int k, int H, hipStream_t stream) {
+  if (T <= 0 || k <= 0 || k > kMaxTopK || H <= 0 || H % 8 != 0) return -1;
+  if (out == nullptr || y == nullptr || w == nullptr || shared == nullptr ||
+      shared_w == nullptr)
+    return -5;
+  const size_t n = (size_t)T * (H / 8);
+  moe_combine_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(
+      y, w, shared, shared_w, out, T, k, H);
   return 0;
 }
 

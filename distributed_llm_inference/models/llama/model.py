@@ -107,22 +107,27 @@ class LlamaBlock(nn.Module):
 
     def quantize_experts_fp8(self) -> "LlamaBlock":
         """fp8 (e4m3, per-row scales) weights for the routed experts of every sparse-MoE layer;
-        attention projections, norms and the router stay bf16."""
+        attention projections, norms, the router, dense layers and the shared expert stay bf16
+        (a block holding only dense layers of a mixed stack is left as it is)."""
         if not self.config.num_experts:
             raise ValueError(f"fp8_experts needs a sparse MoE model; {self.config.name} "
                              f"({self.config.model_type}) has no experts")
-        for layer in self.layers:
-            layer.mlp.quantize_experts_fp8()
+        for layer in self.layers:   # dense layers of a mixed stack have no experts: skipped
+            if layer.is_moe:
+                layer.mlp.quantize_experts_fp8()
         return self
 
     def quantize_experts_mxfp4(self) -> "LlamaBlock":
         """MXFP4 (e2m1, one e8m0 scale per 32 input features) weights for the routed experts of
-        every sparse-MoE layer; attention projections, norms and the router stay bf16."""
+        every sparse-MoE layer; attention projections, norms, the router, dense layers and the
+        shared expert stay bf16 (a block holding only dense layers of a mixed stack is left as
+        it is)."""
         if not self.config.num_experts:
             raise ValueError(f"mxfp4_experts needs a sparse MoE model; {self.config.name} "
                              f"({self.config.model_type}) has no experts")
-        for layer in self.layers:
-            layer.mlp.quantize_experts_mxfp4()
+        for layer in self.layers:   # dense layers of a mixed stack have no experts: skipped
+            if layer.is_moe:
+                layer.mlp.quantize_experts_mxfp4()
         return self
 
     def new_cache(self, window_length: int = 0, num_sink_tokens: int = 0, num_blocks: int = 256,

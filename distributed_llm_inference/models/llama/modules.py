@@ -148,14 +148,17 @@ class LlamaAttention(nn.Module):
 
 
 class LlamaMLP(nn.Module):
-    def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16):
+    def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16,
+                 intermediate_size: Optional[int] = None):
+        """``intermediate_size``: a width other than the spec's (Qwen2-MoE's shared expert)."""
         super().__init__()
         if spec.hidden_act != "silu":
             raise ValueError(f"unsupported Llama activation {spec.hidden_act!r}")
-        self.intermediate_size = spec.intermediate_size
-        self.gate_up_proj = Linear(spec.hidden_size, 2 * spec.intermediate_size, bias=spec.mlp_bias,
+        inter = spec.intermediate_size if intermediate_size is None else int(intermediate_size)
+        self.intermediate_size = inter
+        self.gate_up_proj = Linear(spec.hidden_size, 2 * inter, bias=spec.mlp_bias,
                                    dtype=dtype, device=device)
-        self.down_proj = Linear(spec.intermediate_size, spec.hidden_size, bias=spec.mlp_bias,
+        self.down_proj = Linear(inter, spec.hidden_size, bias=spec.mlp_bias,
                                 dtype=dtype, device=device)
         self.gate_up_proj.role, self.down_proj.role = "gate_up", "down"
         # True once gate_up_proj.weight's rows are in ops.swiglu_interleave order, so the tile
@@ -271,8 +274,8 @@ class LlamaMLP(nn.Module):
 
 
 class MoEMLP(nn.Module):
-    """Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral; HF ``Qwen3MoeSparseMoeBlock``): a bf16
-    router ``gate`` (H -> E), and per token the ``top_k`` most probable of E SwiGLU experts,
+    """Sparse mixture-of-experts MLP (Qwen3-MoE, Mixtral, Qwen2-MoE; HF
+    ``Qwen3MoeSparseMoeBlock``): a bf16 router ``gate`` (H -> E), and per token the ``top_k`` most probable of E SwiGLU experts,
     weighted by their (optionally renormalised) router probabilities.
 
         logits = gate(x)                                   # Linear.forward, bf16
@@ -282,13 +285,27 @@ class MoEMLP(nn.Module):
         out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) # fp32, slot order, one rounding
 
     ``w_gate_up [E, 2I, H]`` holds every expert's rows in ``ops.swiglu_interleave`` order, always
-    (``set_fused_swiglu`` is a no-op); ``w_down [E, H, I]``.  Expert weights are bf16, or after
+    (``set_fused_swiglu`` leaves them alone); ``w_down [E, H, I]``.  Expert weights are bf16, or after
     :meth:`quantize_experts_fp8` e4m3 with one fp32 scale per weight row (``w_gate_up_scale
     [E, 2I]``, ``w_down_scale [E, H]``), or after :meth:`quantize_experts_mxfp4` MXFP4 nibbles
     ``[E, 2I, H / 2]`` / ``[E, H, I / 2]`` with one e8m0 scale per 32 input features
     (``w_gate_up_block_scale [E, 2I, H / 32]``, ``w_down_block_scale [E, H, I / 32]``); the router
     stays bf16 and the activations are never quantised.  The block returns a plain bf16 tensor:
-    nothing is deferred to the next RMSNorm."""
+    nothing is deferred to the next RMSNorm.
+
+    Shared expert (Qwen2-MoE, HF ``Qwen2MoeSparseMoeBlock``; ``spec.shared_expert_intermediate_size
+    > 0``): every token also runs ``shared_expert``, a dense :class:`LlamaMLP` of that width on
+    the dense kernels, scaled by ``sigmoid(shared_expert_gate(x))``.  The gate's one row is stored
+    as row E of ``gate.weight [E + 1, H]``, so the router product yields its logit as column E --
+    one product per layer, no N = 1 launch:
+
+        s      = shared_expert(x)                           # GEMV / tile GEMM, bf16 [T, H]
+        logits = gate(x)                                    # [T, E + 1]
+        route  = ops.moe_route(logits, k, renorm, E)        # shared_w[t] = bf16(sigmoid(logits[t, E]))
+        out[t] = bf16(sum_slot w[t, slot] * y[t k + slot] + shared_w[t] * s[t])
+
+    The shared expert stays bf16 under the expert-only quantisation modes (it is part of
+    "everything but the routed experts")."""
 
     def __init__(self, spec: ModelSpec, device=None, dtype=torch.bfloat16):
         super().__init__()
@@ -300,8 +317,13 @@ class MoEMLP(nn.Module):
         self.norm_topk_prob = spec.norm_topk_prob
         # checkpoint key names: Mixtral's block_sparse_moe.experts.{e}.w1 / w3 / w2
         self.mixtral_keys = spec.model_type == "mixtral"
-        self.gate = Linear(H, E, bias=False, dtype=dtype, device=device)
+        self.shared_size = spec.shared_expert_intermediate_size
+        # rows 0 .. E - 1: the router; with a shared expert, row E: its gate (shared_expert_gate)
+        self.gate = Linear(H, E + (1 if self.shared_size else 0), bias=False, dtype=dtype,
+                           device=device)
         self.gate.role = "router"
+        if self.shared_size:
+            self.shared_expert = LlamaMLP(spec, device, dtype, intermediate_size=self.shared_size)
         self.w_gate_up = nn.Parameter(torch.empty(E, 2 * I, H, dtype=dtype, device=device),
                                       requires_grad=False)
         self.w_down = nn.Parameter(torch.empty(E, H, I, dtype=dtype, device=device),
@@ -357,14 +379,23 @@ class MoEMLP(nn.Module):
         return (w.float() * getattr(self, name + "_scale")[e][:, None]).to(torch.bfloat16)
 
     def set_fused_swiglu(self, on: bool) -> None:
-        """No-op: the grouped GEMM's only epilogue reads interleaved rows."""
+        """No-op for the routed experts: the grouped GEMM's only epilogue reads interleaved
+        rows.  The shared expert is a dense MLP and follows the block's setting."""
+        if self.shared_size:
+            self.shared_expert.set_fused_swiglu(on)
 
     def forward(self, normed: torch.Tensor, x_q=None, defer_reduce: bool = False, norm=None):
         if x_q is not None or norm is not None:
             raise RuntimeError("MoEMLP takes normalised bf16 rows (the layer's generic body)")
+        if not self.shared_size:
+            return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
+                               self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale,
+                               self.w_gate_up_block_scale, self.w_down_block_scale)
+        shared = self.shared_expert(normed)     # a plain bf16 [T, H]: nothing deferred
         return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
                            self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale,
-                           self.w_gate_up_block_scale, self.w_down_block_scale)
+                           self.w_gate_up_block_scale, self.w_down_block_scale,
+                           num_experts=self.num_experts, shared=shared)
 
     # ------------------------------------------------------------------ weights
     def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
@@ -382,7 +413,23 @@ class MoEMLP(nn.Module):
         pre = next((p for p in ("mlp.", "block_sparse_moe.") if p + "gate.weight" in sd), None)
         if pre is None:
             g("block_sparse_moe.gate.weight" if self.mixtral_keys else "mlp.gate.weight")
-        self.gate.weight.copy_(g(pre + "gate.weight").to(dt))
+        router = g(pre + "gate.weight")
+        if tuple(router.shape) != (self.num_experts, self.gate.in_features):
+            raise ValueError(f"{pre}gate.weight {tuple(router.shape)} is not "
+                             f"[{self.num_experts}, {self.gate.in_features}]")
+        self.gate.weight[:self.num_experts].copy_(router.to(dt))
+        if self.shared_size:
+            # Qwen2-MoE: mlp.shared_expert_gate.weight [1, H] becomes row E of the router, and
+            # mlp.shared_expert.* the dense shared MLP
+            self.gate.weight[self.num_experts:].copy_(
+                g(pre + "shared_expert_gate.weight").reshape(1, -1).to(dt))
+            sh = self.shared_expert
+            gu = torch.cat([g(pre + "shared_expert.gate_proj.weight"),
+                            g(pre + "shared_expert.up_proj.weight")], 0)
+            if sh.fused_swiglu:
+                gu = ops.swiglu_interleave(gu)
+            sh.gate_up_proj.weight.copy_(gu.to(dt))
+            sh.down_proj.weight.copy_(g(pre + "shared_expert.down_proj.weight").to(dt))
         if pre + "experts.gate_up_proj" in sd:
             gu, down = g(pre + "experts.gate_up_proj"), g(pre + "experts.down_proj")
             if gu.shape != self.w_gate_up.shape or down.shape != self.w_down.shape:
@@ -405,7 +452,17 @@ class MoEMLP(nn.Module):
         dequantised weights rounded to bf16, MXFP4 experts as their dequantised weights (exact)."""
         pre, names = (("block_sparse_moe.", ("w1", "w3", "w2")) if self.mixtral_keys else
                       ("mlp.", ("gate_proj", "up_proj", "down_proj")))
-        sd = {pre + "gate.weight": self.gate.weight}
+        sd = {pre + "gate.weight": self.gate.weight[:self.num_experts]}
+        if self.shared_size:
+            sh = self.shared_expert
+            gu = sh.gate_up_proj.weight
+            if sh.fused_swiglu:
+                gu = ops.swiglu_deinterleave(gu)
+            gate, up = gu.split([self.shared_size, self.shared_size], 0)
+            sd.update({pre + "shared_expert_gate.weight": self.gate.weight[self.num_experts:],
+                       pre + "shared_expert.gate_proj.weight": gate,
+                       pre + "shared_expert.up_proj.weight": up,
+                       pre + "shared_expert.down_proj.weight": sh.down_proj.weight})
         I = self.intermediate_size
         for e in range(self.num_experts):
             gate, up = ops.swiglu_deinterleave(self._expert_bf16("w_gate_up", e)).split([I, I], 0)
@@ -422,8 +479,10 @@ class LlamaDecoderLayer(nn.Module):
         self.layer_idx = layer_idx
         self.hidden_size = spec.hidden_size
         self.self_attn = LlamaAttention(spec, layer_idx, device, dtype)
-        # sparse MoE (Qwen3-MoE, Mixtral): the layer always takes the generic body below
-        self.is_moe = spec.num_experts > 0
+        # sparse MoE (Qwen3-MoE, Mixtral, Qwen2-MoE's sparse layers): the layer always takes the
+        # generic body below.  A dense layer of a mixed stack is an ordinary dense layer, with
+        # every dense fast path
+        self.is_moe = spec.is_sparse_layer(layer_idx)
         self.mlp = MoEMLP(spec, device, dtype) if self.is_moe else LlamaMLP(spec, device, dtype)
         self.input_layernorm = RMSNorm(spec.hidden_size, spec.rms_norm_eps, device, dtype)
         self.post_attention_layernorm = RMSNorm(spec.hidden_size, spec.rms_norm_eps, device, dtype)

@@ -1373,19 +1373,32 @@ MOE_MAX_TOPK = ref.MOE_MAX_TOPK
 moe_tile_capacity = ref.moe_tile_capacity
 
 
-def moe_topk(logits: torch.Tensor, k: int, renorm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+def moe_topk(logits: torch.Tensor, k: int, renorm: bool, num_experts: Optional[int] = None):
     """Router top-k on ``logits [T, E]`` (bf16): ``(ids [T, k] int32, w [T, k] fp32)`` -- softmax
     in fp32, the k largest in descending order (ties to the lower index), optionally divided by
-    their sum, rounded to bf16 (HF ``Qwen3MoeTopKRouter``)."""
-    T, E = logits.shape
+    their sum, rounded to bf16 (HF ``Qwen3MoeTopKRouter``).
+
+    ``num_experts = E`` (Qwen2-MoE's shared expert): ``logits [T, ld]`` with ``ld > E`` hold the
+    shared expert's gate logit in column E and padding behind it; the result is ``(ids, w,
+    shared_w [T] fp32)`` with ids / w those of ``logits[:, :E]`` and ``shared_w`` the sigmoid of
+    column E rounded to bf16."""
+    T, ld = logits.shape
+    E = ld if num_experts is None else int(num_experts)
     if not 1 <= k <= min(MOE_MAX_TOPK, E) or E > MOE_MAX_EXPERTS:
         raise ValueError(f"moe_topk: E={E} (<= {MOE_MAX_EXPERTS}), k={k} (<= {MOE_MAX_TOPK})")
+    if num_experts is not None and not E < ld:
+        raise ValueError(f"moe_topk: num_experts={E} needs logits with more than num_experts "
+                         f"columns (the gate logit is column {E}), got {ld}")
     if not _gpu(logits):
-        return ref.moe_topk(logits, k, renorm)
+        return ref.moe_topk(logits, k, renorm, num_experts)
     ids = torch.empty(T, k, dtype=torch.int32, device=logits.device)
     w = torch.empty(T, k, dtype=torch.float32, device=logits.device)
-    native().moe_topk(ids, w, logits.contiguous(), bool(renorm))
-    return ids, w
+    if num_experts is None:
+        native().moe_topk(ids, w, logits.contiguous(), bool(renorm))
+        return ids, w
+    shared_w = torch.empty(T, dtype=torch.float32, device=logits.device)
+    native().moe_topk(ids, w, logits.contiguous(), bool(renorm), E, shared_w)
+    return ids, w, shared_w
 
 
 def moe_group(topk_ids: torch.Tensor, topk_w: torch.Tensor, E: int) -> MoERouting:
@@ -1401,11 +1414,16 @@ def moe_group(topk_ids: torch.Tensor, topk_w: torch.Tensor, E: int) -> MoERoutin
     return MoERouting(topk_ids, topk_w, count, offset, pairs, te, ts, tr, nt)
 
 
-def moe_route(logits: torch.Tensor, k: int, renorm: bool) -> MoERouting:
+def moe_route(logits: torch.Tensor, k: int, renorm: bool,
+              num_experts: Optional[int] = None) -> MoERouting:
     """Top-k routing of ``logits [T, E]`` and its grouping by expert, without a host sync (every
-    count stays in device memory; grids depend on (T, E, k) only)."""
-    ids, w = moe_topk(logits, k, renorm)
-    return moe_group(ids, w, logits.shape[1])
+    count stays in device memory; grids depend on (T, E, k) only).  ``num_experts``: as for
+    :func:`moe_topk`; the routing then carries ``shared_w``."""
+    if num_experts is None:
+        ids, w = moe_topk(logits, k, renorm)
+        return moe_group(ids, w, logits.shape[1])
+    ids, w, shared_w = moe_topk(logits, k, renorm, num_experts)
+    return moe_group(ids, w, int(num_experts))._replace(shared_w=shared_w)
 
 
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
@@ -1464,16 +1482,28 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     return out
 
 
-def moe_combine(y: torch.Tensor, topk_w: torch.Tensor,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t * k + slot])``, fp32, in slot order."""
+def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, out: Optional[torch.Tensor] = None,
+                shared: Optional[torch.Tensor] = None,
+                shared_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t * k + slot])``, fp32, in slot order.  With
+    ``shared [T, H]`` (bf16, contiguous) and ``shared_w [T]`` (fp32) the shared expert's term
+    ``shared_w[t] * shared[t]`` is added after the slots, before the one rounding."""
     T = topk_w.shape[0]
+    if (shared is None) != (shared_w is None):
+        raise ValueError("moe_combine: shared and shared_w go together")
     if not _gpu(y):
-        o = ref.moe_combine(y, topk_w)
+        if shared is not None and (shared.dtype != torch.bfloat16
+                                   or tuple(shared.shape) != (T, y.shape[1])
+                                   or tuple(shared_w.shape) != (T,)):
+            raise RuntimeError("moe_combine: shared bf16 [T, H] and shared_w fp32 [T]")
+        o = ref.moe_combine(y, topk_w, shared, shared_w)
         return out.copy_(o) if out is not None else o
     if out is None:
         out = torch.empty(T, y.shape[1], dtype=torch.bfloat16, device=y.device)
-    native().moe_combine(out, y, topk_w.contiguous())
+    if shared is None:
+        native().moe_combine(out, y, topk_w.contiguous())
+    else:
+        native().moe_combine(out, y, topk_w.contiguous(), shared, shared_w)
     return out
 
 
@@ -1482,15 +1512,23 @@ def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
             w_gate_up_scale: Optional[torch.Tensor] = None,
             w_down_scale: Optional[torch.Tensor] = None,
             w_gate_up_block_scale: Optional[torch.Tensor] = None,
-            w_down_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+            w_down_block_scale: Optional[torch.Tensor] = None,
+            num_experts: Optional[int] = None,
+            shared: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
     SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
     expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
     with their row scales ``[E, 2I]`` / ``[E, H]``, or MXFP4 nibbles ``[E, 2I, H / 2]`` /
-    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``."""
-    r = moe_route(gate_logits, k, renorm)
+    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.
+
+    Shared expert (Qwen2-MoE): ``num_experts = E`` and ``shared [T, H]`` (bf16), the shared
+    expert's output, go together; ``gate_logits [T, ld]`` then hold the shared gate's logit in
+    column E (:func:`moe_topk`), and ``sigmoid(logit) * shared`` joins the weighted sum."""
+    if (num_experts is None) != (shared is None):
+        raise ValueError("moe_mlp: num_experts and shared go together")
+    r = moe_route(gate_logits, k, renorm, num_experts)
     h = moe_grouped_gemm(x, w_gate_up, r, w_scale=w_gate_up_scale,
                          w_block_scale=w_gate_up_block_scale)
     y = moe_grouped_gemm(h, w_down, r, down=True, w_scale=w_down_scale,
                          w_block_scale=w_down_block_scale)
-    return moe_combine(y, r.topk_w)
+    return moe_combine(y, r.topk_w, shared=shared, shared_w=r.shared_w)

@@ -386,6 +386,9 @@ class MoERouting(NamedTuple):
     tile_start: torch.Tensor     # [cap]        sorted_pairs, all of expert tile_expert[i]
     tile_rows: torch.Tensor      # [cap]        (1 .. 32 rows); entries past n_tiles are unspecified
     n_tiles: torch.Tensor        # [1] int32
+    # [T] fp32 holding the bf16-rounded sigmoid of the shared expert's gate logit (Qwen2-MoE), or
+    # None: no shared expert
+    shared_w: Optional[torch.Tensor] = None
 
 
 def moe_tile_capacity(T: int, E: int, k: int) -> int:
@@ -393,11 +396,22 @@ def moe_tile_capacity(T: int, E: int, k: int) -> int:
     return min(E, P) + P // MOE_TILE_ROWS
 
 
-def moe_topk(logits: torch.Tensor, k: int, renorm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+def moe_topk(logits: torch.Tensor, k: int, renorm: bool, num_experts: Optional[int] = None):
     """HF ``Qwen3MoeTopKRouter`` on ``logits [T, E]`` (bf16): softmax in fp32, the k largest
     probabilities in descending order, optionally divided by their sum, rounded to bf16.  The
     selection ranks the logits (softmax is monotone) with a stable sort: ties go to the lower
-    expert index, -0 ranks as +0."""
+    expert index, -0 ranks as +0.  Returns ``(ids, w)``.
+
+    ``num_experts = E``: ``logits [T, ld]``, ``ld > E``, carry the shared expert's gate logit in
+    column E (later columns are padding and are not read); ids and w are those of
+    ``logits[:, :E]``, and a third result ``shared_w [T]`` is ``torch.sigmoid`` of the bf16
+    column (HF ``F.sigmoid(shared_expert_gate(x))``, a bf16 value) held as fp32."""
+    if num_experts is not None:
+        if not 0 < num_experts < logits.shape[1]:
+            raise ValueError(f"moe_topk: num_experts={num_experts} needs logits with more than "
+                             f"num_experts columns, got {logits.shape[1]}")
+        ids, w = moe_topk(logits[:, :num_experts], k, renorm)
+        return ids, w, torch.sigmoid(logits[:, num_experts]).float()
     lf = logits.float() + 0.0
     probs = torch.softmax(lf, dim=-1)
     ids = torch.sort(lf, dim=-1, descending=True, stable=True).indices[:, :k]
@@ -471,11 +485,18 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: 
     return out
 
 
-def moe_combine(y: torch.Tensor, topk_w: torch.Tensor) -> torch.Tensor:
-    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t k + slot])`` in fp32, in slot order."""
+def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, shared: Optional[torch.Tensor] = None,
+                shared_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[t] = bf16(sum_slot topk_w[t, slot] * y[t k + slot])`` in fp32, in slot order; with
+    ``shared [T, H]`` (bf16) and ``shared_w [T]`` (fp32) the shared expert's term
+    ``shared_w[t] * shared[t]`` is added after the slots, before the one rounding."""
+    if (shared is None) != (shared_w is None):
+        raise ValueError("moe_combine: shared and shared_w go together")
     T, k = topk_w.shape
     yv = y[:T * k].view(T, k, -1)
     acc = torch.zeros(T, yv.shape[-1], dtype=torch.float32, device=y.device)
     for s in range(k):
         acc += topk_w[:, s, None] * yv[:, s].float()
+    if shared is not None:
+        acc += shared_w.float()[:, None] * shared.float()
     return acc.to(torch.bfloat16)

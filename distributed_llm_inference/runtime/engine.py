@@ -60,6 +60,9 @@ def _activation_reserve(spec: ModelSpec, serve: ServeConfig) -> int:
     per_tok = 2 * (spec.qkv_size + 3 * spec.intermediate_size + 4 * spec.hidden_size)
     if spec.num_experts:   # h and y of the grouped expert GEMMs: k rows per token each
         per_tok += 2 * spec.num_experts_per_tok * (spec.moe_intermediate_size + spec.hidden_size)
+        # the shared expert's gate|up, h and output, alive beside the routed experts' buffers
+        if spec.shared_expert_intermediate_size:
+            per_tok += 2 * (3 * spec.shared_expert_intermediate_size + spec.hidden_size)
     logits = serve.max_batch_size * spec.vocab_size * 4
     return int(T * per_tok * 2 + logits + (2 << 30))
 

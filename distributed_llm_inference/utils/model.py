@@ -175,7 +175,8 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
     ``"fp4"``): OCP MX 4-bit e2m1 weights with one e8m0 scale per 32 input features (17/32 byte
     per parameter; Llama-family blocks) — the interactive-decode and capacity mode.
     ``quantize="fp8_experts"``: sparse-MoE blocks only — the routed experts' weights as fp8 e4m3
-    with one scale per weight row; attention, norms and the router stay bf16.
+    with one scale per weight row; attention, norms, the router, and in Qwen2-MoE models the dense
+    layers and the shared expert, stay bf16.
     ``quantize="mxfp4_experts"``: the same with MXFP4 expert weights (one e8m0 scale per 32 input
     features of a weight row).
     """

@@ -6,6 +6,7 @@ scripts/bench_mxfp4.py's protocol and helpers.
     python3 scripts/bench_moe.py [--models qwen3-30b-a3b,mixtral-8x7b] [--rows 1,8,64,512] [--out DIR]
     python3 scripts/bench_moe.py --fp8 [...]      fp8 expert weights against bf16 -> moe_fp8.json
     python3 scripts/bench_moe.py --fp4 [...]      MXFP4 and fp8 against bf16 -> moe_fp4.json
+    python3 scripts/bench_moe.py --shared [...]   Qwen2-MoE's shared expert -> moe_shared.json
 
 Per model (one layer's shapes) and per decode row count T, with random router logits:
 
@@ -32,6 +33,19 @@ candidates ``moe_fp4`` / ``gate_up_fp4`` / ``down_fp4`` next to the bf16 and fp8
 interleaved in the same process.  Their TB/s is on 17/32 byte per hit expert weight (nibbles and
 block scales); ``vs_fp8`` is the time ratio to the fp8 twin and ``bytes_vs_fp8`` the byte ratio
 it is held against.  Results: ``<out>/moe_fp4.json``.
+
+``--shared`` measures the Qwen2-MoE block (models.llama.modules.MoEMLP with a shared expert;
+default models qwen1.5-moe-a2.7b and qwen2-57b-a14b, rows 1, 4, 32, 512), two ways on the same
+weights, the same graphs over copies, interleaved:
+
+``fused``     the block as the model runs it: the shared gate's row stored behind the router's,
+              its sigmoid taken in moe_topk and the shared term added in moe_combine;
+``unfused``   the composition it replaces: the router product on the E router rows, a separate
+              H -> 1 product with the gate row, ops.moe_mlp without the shared term, then
+              ``sigmoid(g) * s`` and the add as elementwise torch ops.
+
+Both run the same shared expert and the same routed experts; the difference is the N = 1
+product and the two elementwise passes over [T, H].  Results: ``<out>/moe_shared.json``.
 """
 import argparse
 import os
@@ -186,10 +200,90 @@ def bench_model(torch, ops, F, name, rows, res, a):
         torch.cuda.empty_cache()
 
 
+def bench_shared(torch, ops, F, name, rows, res, a):
+    """The Qwen2-MoE block with its shared expert, fused against unfused (module docstring)."""
+    from distributed_llm_inference.config import PRESETS
+    from distributed_llm_inference.models.common import Linear
+    from distributed_llm_inference.models.llama.modules import MoEMLP
+    spec = PRESETS[name]
+    dev = torch.device("cuda", 0)
+    H, I, E, k, S = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
+                     spec.num_experts_per_tok, spec.shared_expert_intermediate_size)
+    layer_bytes = (E * 3 * H * I + 3 * H * S) * 2
+    copies = 8 if layer_bytes < (2 << 30) else 3      # bench_model's rule: past the Infinity Cache
+    gen = torch.Generator(device=dev).manual_seed(1)
+    blocks, routers, gates = [], [], []
+    for _ in range(copies):
+        m = MoEMLP(spec, device=dev)
+        for p_, fan in ((m.gate.weight, H), (m.w_gate_up, H), (m.w_down, I),
+                        (m.shared_expert.gate_up_proj.weight, H),
+                        (m.shared_expert.down_proj.weight, S)):
+            p_.data.normal_(0, fan ** -0.5, generator=gen)
+        m.set_fused_swiglu(True)                      # the engine's setting on the GPU
+        # the unfused composition's two products, on views of the same weight
+        r, g1 = Linear(H, E, device="meta"), Linear(H, 1, device="meta")
+        r.weight = torch.nn.Parameter(m.gate.weight[:E], requires_grad=False)
+        g1.weight = torch.nn.Parameter(m.gate.weight[E:], requires_grad=False)
+        blocks.append(m)
+        routers.append(r)
+        gates.append(g1)
+    for T in rows:
+        x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
+
+        def fused(c):
+            return blocks[c](x)
+
+        def unfused(c):
+            m = blocks[c]
+            s = m.shared_expert(x)
+            y = ops.moe_mlp(x, routers[c](x), m.w_gate_up, m.w_down, k, spec.norm_topk_prob)
+            return y + torch.sigmoid(gates[c](x)) * s
+
+        hit = sum(ops.moe_topk(routers[c](x), k, spec.norm_topk_prob)[0].unique().numel()
+                  for c in range(copies)) / copies
+        f0, u0 = fused(0).float(), unfused(0).float()
+        cands = {"fused": fused, "unfused": unfused,
+                 "shared_expert": lambda c: blocks[c].shared_expert(x)}
+        graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
+                  for n, f in cands.items()}
+        samples = {n: [] for n in cands}
+        for _ in range(7):                            # interleaved: same box, same minute
+            for n in cands:
+                samples[n].append(bm._timed(torch, graphs[n], 10) / copies)
+        touched = (hit * 3 * H * I + 3 * H * S) * 2   # hit experts + the shared expert, bf16
+        row = {"T": T, "hit_experts_per_layer": round(hit, 2), "copies": copies,
+               "weight_MB_touched": round(touched / 1e6, 1),
+               "max_abs_diff_fused_vs_unfused": round((f0 - u0).abs().max().item(), 4),
+               "max_abs_unfused": round(u0.abs().max().item(), 3)}
+        for n in cands:
+            us = statistics.median(samples[n])
+            row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
+                      "max_us": round(max(samples[n]), 2)}
+        for n in ("fused", "unfused"):
+            row[n]["weight_TBps"] = round(touched / row[n]["us"] / 1e6, 3)
+        row["fused_vs_unfused"] = round(row["fused"]["us"] / row["unfused"]["us"], 3)
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "shared": S, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        print(f"{name:18s} T={T:4d} hit {hit:5.1f}  fused {row['fused']['us']:9.2f} us "
+              f"({row['fused']['weight_TBps']:.2f} TB/s)  unfused {row['unfused']['us']:9.2f} us  "
+              f"fused/unfused {row['fused_vs_unfused']:.3f}  shared expert alone "
+              f"{row['shared_expert']['us']:.1f} us", flush=True)
+        bm._save(a, "moe_shared.json", res)
+        del graphs
+        torch.cuda.empty_cache()
+    del blocks, routers, gates
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--models", default="qwen3-30b-a3b,mixtral-8x7b")
-    ap.add_argument("--rows", default="1,8,64,512")
+    ap.add_argument("--models", default=None,
+                    help="default qwen3-30b-a3b,mixtral-8x7b (--shared: qwen1.5-moe-a2.7b,"
+                         "qwen2-57b-a14b)")
+    ap.add_argument("--rows", default=None, help="default 1,8,64,512 (--shared: 1,4,32,512)")
+    ap.add_argument("--shared", action="store_true",
+                    help="Qwen2-MoE's shared expert: the fused block against the unfused "
+                         "composition (moe_shared.json)")
     ap.add_argument("--out", default=os.path.join(bm.REPO, "profiles", "moe"))
     ap.add_argument("--fp8", action="store_true",
                     help="fp8 expert weights against bf16 (moe_fp8.json) instead of moe against loop")
@@ -197,6 +291,11 @@ def main():
                     help="MXFP4 and fp8 expert weights against bf16 (moe_fp4.json)")
     ap.add_argument("--note", default="", help="free text kept in the result file (--fp8 / --fp4)")
     a = ap.parse_args()
+    if a.shared and (a.fp8 or a.fp4):
+        ap.error("--shared measures bf16 weights: not with --fp8 / --fp4")
+    a.models = a.models or ("qwen1.5-moe-a2.7b,qwen2-57b-a14b" if a.shared
+                            else "qwen3-30b-a3b,mixtral-8x7b")
+    a.rows = a.rows or ("1,4,32,512" if a.shared else "1,8,64,512")
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
     import torch.nn.functional as F
@@ -225,10 +324,25 @@ def main():
                        "the bf16 / fp8 twin's time; bytes_vs_fp8 = the byte ratio to the fp8 twin")
         res["candidates"]["moe_fp4 / gate_up_fp4 / down_fp4"] = (
             "the same on ops.quantize_expert_weights_mxfp4 of the same tensors")
-    if (a.fp8 or a.fp4) and a.note:
+    if a.shared:
+        res["unit"] = ("us per MoE block (median of 7 interleaved rounds of 10 graph replays over "
+                       "`copies` blocks); weight_TBps = the hit experts' and the shared expert's "
+                       "bf16 weight bytes / time; fused_vs_unfused = time ratio")
+        res["candidates"] = {
+            "fused": "MoEMLP.forward: shared expert, one router product with the gate row, "
+                     "moe_topk with the gate column, grouped GEMM x 2, moe_combine with the "
+                     "shared term",
+            "unfused": "the same shared expert and routed experts with a separate H -> 1 "
+                       "product, sigmoid * mul and add as torch ops",
+            "shared_expert": "the shared expert's dense MLP alone (part of both)"}
+    if (a.fp8 or a.fp4 or a.shared) and a.note:
         res["note"] = a.note
     with torch.no_grad():
         for name in a.models.split(","):
+            if a.shared:
+                bench_shared(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
+                             res, a)
+                continue
             bench_model(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")], res, a)
     return 0
 
