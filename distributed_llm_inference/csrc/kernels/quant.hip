@@ -10,6 +10,11 @@
 namespace dli {
 
 constexpr float kFp8Max = 448.f;
+// Floor of a row's dynamic scale (FLT_MIN).  A row with 0 < amax < ~1.3e-36 has a subnormal
+// amax / 448 whose reciprocal is inf: its nonzero elements would saturate and its zeros become
+// 0 * inf = NaN, which fmaxf turns into -448.  With the floor such a row quantises towards zero
+// instead; every row with amax >= 448 FLT_MIN keeps amax / 448 bit for bit.
+constexpr float kScaleMin = 1.17549435e-38f;
 
 // One workgroup per row; threads chosen so each holds <= 4 bf16x8 vectors (<= 1024 threads): a
 // 28672-wide row (70B down-projection input) gets 896 threads x 4 vectors instead of 256 x 14,
@@ -33,7 +38,7 @@ __device__ __forceinline__ void store_fp8_row(float (&v)[VPT][8], uint8_t* __res
 #pragma unroll
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[i][j]));
   amax = block_reduce_max(amax, scratch);
-  const float s = amax > 0.f ? amax / kFp8Max : 1.f;
+  const float s = amax > 0.f ? fmaxf(amax / kFp8Max, kScaleMin) : 1.f;
   const float inv = 1.f / s;
   if (threadIdx.x == 0) *srow = s;
   uint2* qr = reinterpret_cast<uint2*>(qrow);
@@ -176,7 +181,7 @@ __global__ void __launch_bounds__(1024) quant_rowwise_int8_kernel(
     }
   }
   amax = block_reduce_max(amax, scratch);
-  const float s = amax > 0.f ? amax / 127.f : 1.f;
+  const float s = amax > 0.f ? fmaxf(amax / 127.f, kScaleMin) : 1.f;
   const float inv = 1.f / s;
   if (threadIdx.x == 0) scale[row] = s;
   uint2* qr = reinterpret_cast<uint2*>(q + (size_t)row * K);

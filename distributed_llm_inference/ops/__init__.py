@@ -466,10 +466,13 @@ def silu_mul_quant(x: torch.Tensor):
     return q, s
 
 
+ROW_SCALE_MIN = 2.0 ** -126   # FLT_MIN: floor of a row's dynamic scale, so 1 / scale is finite
+
+
 def _quant_ref(x2: torch.Tensor, shape):
     xf = x2.float()
-    s = xf.abs().amax(-1).clamp_min(1e-12) / FP8_MAX
-    s = torch.where(xf.abs().amax(-1) > 0, s, torch.ones_like(s))
+    amax = xf.abs().amax(-1)
+    s = torch.where(amax > 0, (amax / FP8_MAX).clamp_min(ROW_SCALE_MIN), torch.ones_like(amax))
     q = (xf / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
     return q.reshape(shape), s.reshape(-1, 1)
 
@@ -799,8 +802,8 @@ def quant_rowwise_int8(x: torch.Tensor, outlier: Optional[torch.Tensor] = None
         xf = x.float()
         if outlier is not None:
             xf = xf * (outlier == 0).to(xf.dtype)
-        s = xf.abs().amax(-1).clamp_min(0)
-        s = torch.where(s > 0, s / 127.0, torch.ones_like(s))
+        s = xf.abs().amax(-1)
+        s = torch.where(s > 0, (s / 127.0).clamp_min(ROW_SCALE_MIN), torch.ones_like(s))
         return torch.round(xf / s[:, None]).clamp(-127, 127).to(torch.int8), s
     q = torch.empty(rows, K, dtype=torch.int8, device=x.device)
     s = torch.empty(rows, dtype=torch.float32, device=x.device)

@@ -37,7 +37,11 @@ def layer_norm(x, w, b, eps, residual=None, residual_out=None):
         dst = residual if residual_out is None else residual_out
         dst.copy_((x.float() + residual.float()).to(residual.dtype))
         x = residual = dst
-    y = F.layer_norm(x.float(), (x.shape[-1],), w.float(), b.float(), eps)
+    # two passes in fp32, as layer_norm_kernel: F.layer_norm's chunked Welford mean is off by
+    # several 2^-18 mean|x| on a row whose one large element comes last
+    xf = x.float()
+    d = xf - xf.mean(-1, keepdim=True)
+    y = d * torch.rsqrt((d * d).mean(-1, keepdim=True) + eps) * w.float() + b.float()
     return y.to(x.dtype), residual
 
 
