@@ -32,7 +32,7 @@ KERNEL_SOURCES = ["kernels/norm.hip", "kernels/activation.hip", "kernels/rope_ca
                   "kernels/attention.hip", "kernels/attn_prefill32.hip", "kernels/sampling.hip", "kernels/quant.hip",
                   "kernels/gemv.hip", "kernels/gemm_tile.hip", "kernels/gemm4.hip",
                   "kernels/gemm_fp4.hip", "kernels/gemm_fp4_small.hip", "kernels/gemm_fp8_small.hip",
-                  "kernels/moe.hip", "kernels/int8_outlier.hip", "kernels/digest.hip"]
+                  "kernels/moe.hip", "kernels/moe_tile.hip", "kernels/int8_outlier.hip", "kernels/digest.hip"]
 TORCH_SOURCES = ["bindings.hip", "comm/rccl_p2p.hip", "comm/streams.hip"]
 RUNTIME_SOURCES = ["runtime/block_manager.cpp", "runtime/shm_channel.cpp"]
 

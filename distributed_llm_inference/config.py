@@ -705,6 +705,12 @@ class KernelPolicy:
     # the rows for torch._scaled_mm or the block-scaled tile GEMM.  0 = off, else 3..32
     # (docs/kernels.md "fp8 weights, 3-32 rows" has the measured crossover)
     fp8_small_m: int = 0
+    # sparse MoE, bf16 experts: calls whose mean rows per expert T k / E reach this many run the
+    # routed experts on the grouped MFMA tile GEMM (csrc/kernels/moe_tile.hip: 128-row tiles, a
+    # weight byte read once per 128 rows) instead of the weight-streaming kernel's 32-row tiles.
+    # 0 = off, else 32..1024 (docs/kernels.md "Sparse MoE: tile GEMM" has the measured
+    # crossover); fp8 / MXFP4 experts and the CPU path ignore it
+    moe_tile_rows: int = 0
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 
@@ -713,6 +719,8 @@ class KernelPolicy:
             raise ValueError(f"fp4_small_m={self.fp4_small_m}: 0 (off) or 3..32")
         if self.fp8_small_m != 0 and not 3 <= self.fp8_small_m <= 32:
             raise ValueError(f"fp8_small_m={self.fp8_small_m}: 0 (off) or 3..32")
+        if self.moe_tile_rows != 0 and not 32 <= self.moe_tile_rows <= 1024:
+            raise ValueError(f"moe_tile_rows={self.moe_tile_rows}: 0 (off) or 32..1024")
         if self.gemm4_decode_sched not in (4, 6, 8, 9):
             raise ValueError(f"gemm4_decode_sched={self.gemm4_decode_sched}: 4, 6, 8 or 9")
         sel = self.fp8_gemm4

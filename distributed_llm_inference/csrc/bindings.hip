@@ -1151,6 +1151,45 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
                                         (int)epilogue, cur_stream()), "moe_grouped_gemm");
 }
 
+// moe_grouped_gemm's products for bf16 W on the tile kernel (moe_tile.hip): 128-row tiles derived
+// in the kernel from expert_count [E] / expert_offset [E + 1]; N % 128 == 0, K % 64 == 0
+void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor expert_count,
+                   Tensor expert_offset, int64_t T, int64_t k, int64_t epilogue) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
+  CHECK_BF16(out); CHECK_BF16(x);
+  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
+  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16,
+              "moe_tile_gemm: bf16 expert weights only (fp8 / MXFP4 experts run on "
+              "moe_grouped_gemm)");
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
+              "moe_tile_gemm: out / x 2-D, w [E, N, K]");
+  TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_tile_gemm: epilogue 0 (gate|up) or 1 (down)");
+  const int64_t E = w.size(0), N = w.size(1), K = w.size(2);
+  TORCH_CHECK(T >= 1 && T <= (1 << 24) && E >= 1 && E <= 256 && k >= 1 && k <= 8,
+              "moe_tile_gemm: 1 <= T <= 2^24, E <= 256, k <= 8");
+  const int64_t P = T * k;
+  TORCH_CHECK(dli::moe_tile_gemm_capacity((int)T, (int)E, (int)k) <= 65535,
+              "moe_tile_gemm: more than 65535 tiles (T * k too large for one launch)");
+  TORCH_CHECK(sorted_pairs.numel() == P && expert_count.numel() == E &&
+                  expert_offset.numel() == E + 1,
+              "moe_tile_gemm: sorted_pairs [T k], expert_count [E], expert_offset [E + 1]");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= (1 << 24), "moe_tile_gemm: needs K % 64 == 0");
+  TORCH_CHECK(N >= 128 && N % 128 == 0 && N <= (1 << 24), "moe_tile_gemm: needs N % 128 == 0");
+  TORCH_CHECK(x.size(1) == K && x.size(0) >= (epilogue == 0 ? T : P),
+              "moe_tile_gemm: x [T, K] (gate|up) or [>= T k, K] (down)");
+  TORCH_CHECK(out.size(0) >= P && out.size(1) == (epilogue == 0 ? N / 2 : N),
+              "moe_tile_gemm: out [>= T k, N / 2] (gate|up) or [>= T k, N] (down)");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
+                  sorted_pairs.device() == x.device() && expert_count.device() == x.device() &&
+                  expert_offset.device() == x.device(), "moe_tile_gemm: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_moe_tile_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
+                                     expert_count.data_ptr<int>(), expert_offset.data_ptr<int>(),
+                                     (int)T, (int)E, (int)k, (int)N, (int)K, (int)epilogue,
+                                     cur_stream()), "moe_tile_gemm");
+}
+
 // shared [T, H] (bf16) with shared_w [T] (fp32): the shared expert's term, added after the slots
 void moe_combine(Tensor out, Tensor y, Tensor w, optional<Tensor> shared,
                  optional<Tensor> shared_w) {
@@ -1442,6 +1481,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tile_expert"), py::arg("tile_start"), py::arg("tile_rows"), py::arg("n_tiles"),
         py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none(),
         py::arg("w_block_scale") = py::none());
+  m.def("moe_tile_gemm", &moe_tile_gemm,
+        "grouped MFMA tile GEMM over the routed bf16 experts, <= 128-row tiles (0: gate|up + "
+        "SwiGLU, 1: down)",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
+        py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
+        py::arg("epilogue"));
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"), py::arg("shared") = py::none(),
         py::arg("shared_w") = py::none());

@@ -208,6 +208,15 @@ int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, con
                                 const int* tile_start, const int* tile_rows, const int* n_tiles,
                                 int cap, int T, int E, int k, int N, int K, int epilogue,
                                 hipStream_t stream);
+// Grouped MFMA tile GEMM for experts with many rows (moe_tile.hip): the products of
+// launch_moe_grouped_gemm (bf16 W [E, N, K], the same two epilogues, x and out as there) on tiles
+// of <= 128 rows x 128 weight rows staged in LDS; N % 128 == 0, K % 64 == 0.  The 128-row tiles
+// are derived in the kernel from expert_count [E] / expert_offset [E + 1] (launch_moe_group's);
+// the grid is (N / 128, moe_tile_gemm_capacity) = min(E, P) + P / 128 row tiles
+int moe_tile_gemm_capacity(int T, int E, int k);
+int launch_moe_tile_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+                         const int* expert_count, const int* expert_offset, int T, int E, int k,
+                         int N, int K, int epilogue, hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

@@ -1,0 +1,237 @@
+// Sparse mixture-of-experts MLP, experts with many rows: a grouped MFMA tile GEMM over the routed
+// experts' bf16 weights.  moe.hip's grouped kernel streams an expert's weights once per tile of
+// <= 32 rows, which is the right shape for decode rows and the wrong one once an expert has
+// hundreds (prefill chunks, Mixtral at a 512-sequence micro-batch): here a workgroup multiplies a
+// tile of <= 128 rows of sorted_pairs with 128 weight rows of the tile's expert, both operands
+// staged in LDS, so a weight byte is read once per 128 rows.
+//
+//   * grid (N / 128, min(E, P) + P / 128), fixed by (T, E, k, N) alone; workgroup (nb, tile).
+//     The 128-row tiles are not in the routing tables (those stay moe_group's 32-row tiles): every
+//     wave derives its tile from expert_count in a prologue of its own -- lane l holds experts
+//     4 l .. 4 l + 3 (E <= 256), the tiles ceil(count / 128) of the lanes are prefix-summed across
+//     the wave, and the one lane whose range holds the tile index finds the expert and the tile's
+//     number inside it.  A tile index past the sum returns before any DMA or barrier.  Every value
+//     is clamped before it forms an address (counts into [0, P], expert into [0, E), rows into
+//     [1, 128], start + rows <= P, pair < P hence token < T).
+//   * 4 waves as 2 (weight rows) x 2 (activation rows), 64 x 64 per wave = 4 x 4 fragments of
+//     v_mfma_f32_16x16x32_bf16 with the weight as the A operand (the accumulator holds the tile
+//     transposed: a lane owns 4 consecutive output columns of one row).
+//   * k-step of 64 (128 bytes of every row).  Both operand tiles [128 rows][128 B] are staged by
+//     16-byte LDS-DMA, lane-linear in LDS; 16-byte chunk c of row r sits in slot c ^ ((r >> 1) & 7)
+//     -- gemm_tile.hip's swizzle, applied to the per-lane source address -- so the fragment
+//     ds_read_b128s are conflict-free.  The activation rows are gathered: the source address is
+//     per lane already, so a gathered row is only a different pointer.  Image rows past the
+//     tile's count repeat its last row (loaded in bounds, computed, never stored).
+//   * two LDS buffers of 32 KB (weight | activation tile), one barrier per k-step:
+//         wait for k-step t's DMA, barrier; send k-step t + 1 into the other buffer; multiply t
+//     the barrier also says that every wave is done reading the other buffer (k-step t - 1).  Any
+//     number of k-steps >= 1 (K % 64 == 0).  Two workgroups per CU overlap one's wait with the
+//     other's MFMAs.
+//   * epilogue 0 (gate|up): gate and up of an output column are 16 rows apart inside every
+//     aligned 32-row block of the swiglu_interleave'd weight, i.e. A fragments 2 p and 2 p + 1 of
+//     a wave: the lane holds both; gate and up rounded to bf16, silu(gate) * up in fp32, rounded;
+//     h[start + r, I].  epilogue 1 (down): row r goes to y[sorted_pairs[start + r], H].
+//   * no atomics; a row's result depends on that row and its expert only (the k order is fixed).
+#include "kernels.h"
+
+namespace dli {
+
+namespace {
+
+constexpr int kMaxExperts = 256;
+constexpr int kMaxTopK = 8;
+constexpr int kTM = 128;          // activation rows per tile
+constexpr int kTN = 128;          // weight rows per workgroup
+constexpr int kBK = 64;           // k per step
+constexpr int kThreads = 256;
+constexpr int kOp = 128 * 128;    // bytes of one staged operand tile
+constexpr int kBuf = 2 * kOp;     // weight tile | activation tile
+
+enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
+
+typedef __attribute__((address_space(3))) void lds_void_mt;
+typedef __attribute__((address_space(1))) void gbl_void_mt;
+
+// 16 bytes per lane global -> LDS (LDS-DMA): the wave's 64 lanes fill 1 KB at `lds_wave_base`
+__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gbl_void_mt*)g, (lds_void_mt*)lds_wave_base, 16, 0, 0);
+}
+
+template <int EPI>
+__global__ void __launch_bounds__(kThreads, 2)
+moe_tile_gemm_kernel(const bf16* __restrict__ x, const bf16* __restrict__ W,
+                     bf16* __restrict__ out, const int* __restrict__ sorted_pairs,
+                     const int* __restrict__ expert_count, const int* __restrict__ expert_offset,
+                     int E, int topk, int P, int N, int K) {
+  __shared__ __attribute__((aligned(1024))) char smem[2 * kBuf];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.y, nb = blockIdx.x;
+
+  // ---- which expert, which rows: the wave's prefix sum over ceil(count / 128) ----
+  int cnt[4], nt[4], mine_tiles = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = 4 * lane + q;
+    cnt[q] = j < E ? min(max(expert_count[j], 0), P) : 0;
+    nt[q] = (cnt[q] + kTM - 1) / kTM;
+    mine_tiles += nt[q];
+  }
+  int incl = mine_tiles;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (tile >= __shfl(incl, 63, 64)) return;   // before any DMA or barrier; the same in every wave
+  int rem = tile - (incl - mine_tiles), e_l = 4 * lane, c_l = cnt[0];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    if (e_l == 4 * lane + q && rem >= nt[q]) {
+      rem -= nt[q];
+      e_l = 4 * lane + q + 1;
+      c_l = cnt[q + 1];
+    }
+  }
+  const unsigned long long own = __ballot(incl - mine_tiles <= tile && tile < incl);
+  const int owner = own ? __builtin_ctzll(own) : 0;   // exactly one lane (tile < the sum)
+  const int e = min(max(__builtin_amdgcn_readlane(e_l, owner), 0), E - 1);
+  const int ti = max(__builtin_amdgcn_readlane(rem, owner), 0);
+  const int ce = __builtin_amdgcn_readlane(c_l, owner);
+  const int rows = min(max(ce - kTM * ti, 1), min(kTM, P));
+  const int start = min(max(expert_offset[e] + kTM * ti, 0), P - rows);
+  const int* pairs = sorted_pairs + start;
+  const bf16* We = W + (size_t)e * N * K;
+  const int n0 = nb * kTN;
+  const int kt = K / kBK;
+
+  // ---- staging: DMA round j fills image rows 32 j .. 32 j + 31 of an operand tile (thread: row
+  // 32 j + (tid >> 3), slot tid & 7); the chunk that belongs in that slot is the same every round
+  const int srow = tid >> 3;
+  const int chunk = (tid & 7) ^ ((srow >> 1) & 7);
+  const bf16* wsrc = We + (size_t)(n0 + srow) * K + chunk * 8;
+  const bf16* xsrc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int tr = min(32 * j + srow, rows - 1);
+    size_t src;
+    if constexpr (EPI == kMoeGateUp) src = (size_t)(min(max(pairs[tr], 0), P - 1) / topk);   // token
+    else src = (size_t)(start + tr);                                                        // h row
+    xsrc[j] = x + src * K + chunk * 8;
+  }
+  auto stage = [&](int t, int buf) {
+    char* dst = smem + buf * kBuf + wave * 1024;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      glds16(wsrc + (size_t)j * 32 * K + (size_t)t * kBK, dst + j * 4096);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) glds16(xsrc[j] + (size_t)t * kBK, dst + kOp + j * 4096);
+  };
+
+  // ---- fragments: lane (fr, g) reads chunk 4 kk + g of row 16 f + fr of its wave's 64 rows ----
+  const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, g = lane >> 4;
+  int foff[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) foff[kk] = fr * 128 + (((4 * kk + g) ^ ((fr >> 1) & 7)) << 4);
+  const int aoff = wr * 64 * 128, boff = kOp + wc * 64 * 128;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  stage(0, 0);
+  for (int t = 0; t < kt; ++t) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();   // k-step t has landed for every wave; nobody still reads the other buffer
+    if (t + 1 < kt) stage(t + 1, (t + 1) & 1);
+    asm volatile("" ::: "memory");
+    const char* buf = smem + (t & 1) * kBuf;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 af[4], bfr[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        af[f] = *reinterpret_cast<const bf16x8*>(buf + aoff + f * 2048 + foff[kk]);
+        bfr[f] = *reinterpret_cast<const bf16x8*>(buf + boff + f * 2048 + foff[kk]);
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
+    }
+    asm volatile("" ::: "memory");   // the next DMA into this buffer stays behind its reads
+  }
+
+  // ---- epilogue: acc[a][b][i] = y[m = 64 wc + 16 b + fr][n = n0 + 64 wr + 16 a + 4 g + i] ----
+  if constexpr (EPI == kMoeGateUp) {
+    const int I = N >> 1;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int m = 64 * wc + 16 * b + fr;
+      if (m >= rows) continue;
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        bf16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float gt = (float)(bf16)acc[2 * p][b][i];
+          const float up = (float)(bf16)acc[2 * p + 1][b][i];
+          o[i] = (bf16)(silu(gt) * up);
+        }
+        // weight rows 32 q .. 32 q + 31 are gate | up of output columns 16 q .. 16 q + 15
+        const int col = ((n0 + 64 * wr + 32 * p) >> 1) + 4 * g;
+        *reinterpret_cast<bf16x4*>(out + (size_t)(start + m) * I + col) = o;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int m = 64 * wc + 16 * b + fr;
+      if (m >= rows) continue;
+      const size_t dst = (size_t)min(max(pairs[m], 0), P - 1);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        bf16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = (bf16)acc[a][b][i];
+        *reinterpret_cast<bf16x4*>(out + dst * N + n0 + 64 * wr + 16 * a + 4 * g) = o;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+int moe_tile_gemm_capacity(int T, int E, int k) {
+  const long P = (long)T * k;
+  return (int)((E < P ? E : P) + P / kTM);
+}
+
+int launch_moe_tile_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+                         const int* expert_count, const int* expert_offset, int T, int E, int k,
+                         int N, int K, int epilogue, hipStream_t stream) {
+  if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK) return -1;
+  if (N <= 0 || N % kTN != 0 || K <= 0 || K % kBK != 0) return -2;
+  if ((long)T * k > (1L << 30)) return -3;
+  const int cap = moe_tile_gemm_capacity(T, E, k);
+  if (cap <= 0 || cap > 65535) return -3;
+  if (out == nullptr || x == nullptr || W == nullptr || sorted_pairs == nullptr ||
+      expert_count == nullptr || expert_offset == nullptr)
+    return -5;
+  const dim3 grid(N / kTN, cap);
+  const int P = T * k;
+  if (epilogue == kMoeGateUp)
+    moe_tile_gemm_kernel<kMoeGateUp><<<grid, kThreads, 0, stream>>>(
+        x, W, out, sorted_pairs, expert_count, expert_offset, E, k, P, N, K);
+  else if (epilogue == kMoeDown)
+    moe_tile_gemm_kernel<kMoeDown><<<grid, kThreads, 0, stream>>>(
+        x, W, out, sorted_pairs, expert_count, expert_offset, E, k, P, N, K);
+  else
+    return -4;
+  return 0;
+}
+
+}  // namespace dli

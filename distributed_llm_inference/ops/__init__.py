@@ -1429,10 +1429,29 @@ def moe_route(logits: torch.Tensor, k: int, renorm: bool,
     return moe_group(ids, w, int(num_experts))._replace(shared_w=shared_w)
 
 
+def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
+    """Whether a sparse-MoE call of T tokens, top-k of E experts runs its routed experts on the
+    grouped MFMA tile GEMM (moe_tile.hip) instead of the weight-streaming kernel (moe.hip):
+    ``KernelPolicy.moe_tile_rows`` is set, the expert weights are bf16 (``weight_format``:
+    "bf16", "fp8" or "mxfp4"), the call is on the GPU (``device``: the activations'), and the
+    mean rows per expert reach the threshold, ``T k >= moe_tile_rows E``.  Host-known integers
+    only: no device sync."""
+    rows = policy().moe_tile_rows
+    return bool(rows and torch.device(device).type == "cuda" and weight_format == "bf16"
+                and T * k >= rows * E)
+
+
+def _moe_weight_format(w: torch.Tensor, w_scale, w_block_scale) -> str:
+    if w_block_scale is not None or w.dtype == torch.uint8:
+        return "mxfp4"
+    return "bf16" if w_scale is None and w.dtype == torch.bfloat16 else "fp8"
+
+
 def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
                      w_scale: Optional[torch.Tensor] = None,
-                     w_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     w_block_scale: Optional[torch.Tensor] = None,
+                     tiles: Optional[bool] = None) -> torch.Tensor:
     """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
     ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
     rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
@@ -1442,9 +1461,19 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     e4m3fn (:func:`quantize_expert_weights_fp8`): the row scale multiplies the fp32 product, the
     activations stay bf16.  With ``w_block_scale [E, N, K / 32]`` (uint8 e8m0) ``w`` is MXFP4
     nibbles ``uint8 [E, N, K / 2]`` (:func:`quantize_expert_weights_mxfp4`), widened exactly to
-    bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights."""
+    bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights.
+
+    ``tiles``: True runs the grouped MFMA tile GEMM (moe_tile.hip: bf16 weights on the GPU,
+    N % 128 == 0, K % 64 == 0; the same products, another K summation order), False the
+    weight-streaming kernel, None lets :func:`moe_uses_tiles` decide.  The CPU path ignores it."""
     T, k = r.topk_ids.shape
     P, N = T * k, w.shape[1]
+    fmt = _moe_weight_format(w, w_scale, w_block_scale)
+    if tiles is None:
+        tiles = moe_uses_tiles(T, k, w.shape[0], fmt, x.device)
+    elif tiles and _gpu(x) and fmt != "bf16":
+        raise ValueError(f"moe_grouped_gemm: tiles=True needs bf16 expert weights, got {fmt} "
+                         "(quantised experts run on the weight-streaming kernel)")
     if w_block_scale is not None or w.dtype == torch.uint8:
         if w_scale is not None:
             raise ValueError("moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both")
@@ -1471,6 +1500,10 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
             raise ValueError("moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with "
                              "w_scale [E, N]")
         return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale, w_block_scale)
+    if tiles:
+        native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
+                               r.expert_offset, T, k, 1 if down else 0)
+        return out
     if w_block_scale is not None:
         native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
                                   r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0,
@@ -1522,7 +1555,8 @@ def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
     SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
     expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
     with their row scales ``[E, 2I]`` / ``[E, H]``, or MXFP4 nibbles ``[E, 2I, H / 2]`` /
-    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.
+    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.  bf16
+    experts with many rows each run both products on the tile GEMM (:func:`moe_uses_tiles`).
 
     Shared expert (Qwen2-MoE): ``num_experts = E`` and ``shared [T, H]`` (bf16), the shared
     expert's output, go together; ``gate_logits [T, ld]`` then hold the shared gate's logit in

@@ -395,9 +395,10 @@ class MoERouting(NamedTuple):
     shared_w: Optional[torch.Tensor] = None
 
 
-def moe_tile_capacity(T: int, E: int, k: int) -> int:
+def moe_tile_capacity(T: int, E: int, k: int, tile_rows: int = MOE_TILE_ROWS) -> int:
+    """Tiles of <= ``tile_rows`` rows that P = T k pairs over E experts can need, at most."""
     P = T * k
-    return min(E, P) + P // MOE_TILE_ROWS
+    return min(E, P) + P // tile_rows
 
 
 def moe_topk(logits: torch.Tensor, k: int, renorm: bool, num_experts: Optional[int] = None):
@@ -425,9 +426,11 @@ def moe_topk(logits: torch.Tensor, k: int, renorm: bool, num_experts: Optional[i
     return ids.to(torch.int32), w.to(torch.bfloat16).float()
 
 
-def moe_group(topk_ids: torch.Tensor, E: int):
+def moe_group(topk_ids: torch.Tensor, E: int, tile_rows: int = MOE_TILE_ROWS):
     """Group the P pairs of ``topk_ids [T, k]`` by expert: counts, offsets, the stable sort of the
-    pair indices by expert and its cut into tiles of <= 32 rows (ids clamped into [0, E))."""
+    pair indices by expert and its cut into tiles of <= ``tile_rows`` rows (32: the routing
+    tables; 128: the tiles csrc/kernels/moe_tile.hip derives from the counts).  Ids are clamped
+    into [0, E)."""
     T, k = topk_ids.shape
     P = T * k
     dev = topk_ids.device
@@ -436,16 +439,16 @@ def moe_group(topk_ids: torch.Tensor, E: int):
     offset = torch.zeros(E + 1, dtype=torch.long, device=dev)
     offset[1:] = count.cumsum(0)
     sorted_pairs = torch.sort(flat, stable=True).indices
-    ntile = (count + MOE_TILE_ROWS - 1) // MOE_TILE_ROWS
+    ntile = (count + tile_rows - 1) // tile_rows
     tile_expert = torch.repeat_interleave(torch.arange(E, device=dev), ntile)
     n = tile_expert.numel()
     first = ntile.cumsum(0) - ntile
     within = torch.arange(n, device=dev) - first[tile_expert]
-    cap = moe_tile_capacity(T, E, k)
+    cap = moe_tile_capacity(T, E, k, tile_rows)
     tabs = torch.zeros(3, cap, dtype=torch.int32, device=dev)
     tabs[0, :n] = tile_expert
-    tabs[1, :n] = offset[tile_expert] + MOE_TILE_ROWS * within
-    tabs[2, :n] = torch.clamp(count[tile_expert] - MOE_TILE_ROWS * within, max=MOE_TILE_ROWS)
+    tabs[1, :n] = offset[tile_expert] + tile_rows * within
+    tabs[2, :n] = torch.clamp(count[tile_expert] - tile_rows * within, max=tile_rows)
     i32 = torch.int32
     return (count.to(i32), offset.to(i32), sorted_pairs.to(i32), tabs[0], tabs[1], tabs[2],
             torch.tensor([n], dtype=i32, device=dev))

@@ -7,6 +7,7 @@ scripts/bench_mxfp4.py's protocol and helpers.
     python3 scripts/bench_moe.py --fp8 [...]      fp8 expert weights against bf16 -> moe_fp8.json
     python3 scripts/bench_moe.py --fp4 [...]      MXFP4 and fp8 against bf16 -> moe_fp4.json
     python3 scripts/bench_moe.py --shared [...]   Qwen2-MoE's shared expert -> moe_shared.json
+    python3 scripts/bench_moe.py --tile [...]     the tile GEMM for many rows per expert -> moe_tile.json
 
 Per model (one layer's shapes) and per decode row count T, with random router logits:
 
@@ -46,6 +47,14 @@ weights, the same graphs over copies, interleaved:
 
 Both run the same shared expert and the same routed experts; the difference is the N = 1
 product and the two elementwise passes over [T, H].  Results: ``<out>/moe_shared.json``.
+
+``--tile`` measures the grouped MFMA tile GEMM (csrc/kernels/moe_tile.hip, bf16 experts; default
+rows 64, 512, 2048, 8192): ``moe`` (route, both products on the weight-streaming kernel, combine),
+``moe_tile`` (the same launches with both products on the tile kernel) and ``loop``, plus the two
+products alone on either kernel (``gate_up`` / ``down`` and ``gate_up_tile`` / ``down_tile``), the
+same graphs over copies, interleaved.  Reported besides the times: achieved TFLOP/s from the
+shapes (6 T k H I per layer), the time ratios, and whether the min-max ranges of the two kernels
+are apart (``separated``).  Results: ``<out>/moe_tile.json``.
 """
 import argparse
 import os
@@ -200,6 +209,106 @@ def bench_model(torch, ops, F, name, rows, res, a):
         torch.cuda.empty_cache()
 
 
+def bench_tile(torch, ops, F, name, rows, res, a):
+    """The grouped MFMA tile GEMM against the weight-streaming kernel and the expert loop (module
+    docstring, ``--tile``)."""
+    from distributed_llm_inference.config import PRESETS
+    spec = PRESETS[name]
+    dev = torch.device("cuda", 0)
+    H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
+                  spec.num_experts_per_tok)
+    copies = 8 if E * 3 * H * I * 2 < (2 << 30) else 3   # bench_model's rule
+    gen = torch.Generator(device=dev).manual_seed(1)
+    wgu = [torch.empty(E, 2 * I, H, device=dev, dtype=torch.bfloat16).normal_(0, H ** -0.5, generator=gen)
+           for _ in range(copies)]
+    wd = [torch.empty(E, H, I, device=dev, dtype=torch.bfloat16).normal_(0, I ** -0.5, generator=gen)
+          for _ in range(copies)]
+    for T in rows:
+        x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
+        logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
+                  for _ in range(copies)]
+        routes = [ops.moe_route(lg, k, spec.norm_topk_prob) for lg in logits]
+        hit_total, loops = 0, []
+        for c in range(copies):                      # host-side routing of the baseline: not timed
+            ids, w = routes[c].topk_ids.cpu(), routes[c].topk_w.cpu()
+            per = []
+            for e in ids.unique().tolist():
+                tok, slot = (ids == e).nonzero(as_tuple=True)
+                per.append((e, tok.to(dev), w[tok, slot].to(dev)[:, None]))
+            hit_total += len(per)
+            loops.append(per)
+        hit = hit_total / copies
+        touched = hit * 3 * H * I * 2                 # expert bytes one layer streams
+
+        def moe_with(tiles):
+            def run(c):
+                r = ops.moe_route(logits[c], k, spec.norm_topk_prob)
+                h = ops.moe_grouped_gemm(x, wgu[c], r, tiles=tiles)
+                y = ops.moe_grouped_gemm(h, wd[c], r, down=True, tiles=tiles)
+                return ops.moe_combine(y, r.topk_w)
+            return run
+
+        def loop(c):
+            acc = torch.zeros(T, H, device=dev, dtype=torch.float32)
+            for e, tok, we in loops[c]:
+                h = ops.swiglu_interleaved(F.linear(x.index_select(0, tok), wgu[c][e]))
+                acc.index_add_(0, tok, F.linear(h, wd[c][e]).float() * we)
+            return acc.to(torch.bfloat16)
+
+        ref = loop(0).float()
+        err = {n: (moe_with(t)(0).float() - ref).abs().max().item()
+               for n, t in (("moe", False), ("moe_tile", True))}
+        hs = [ops.moe_grouped_gemm(x, wgu[c], routes[c], tiles=False) for c in range(copies)]
+        ys = [ops.moe_grouped_gemm(hs[c], wd[c], routes[c], down=True, tiles=False)
+              for c in range(copies)]
+        cands = {"moe": moe_with(False), "moe_tile": moe_with(True), "loop": loop}
+        for n, t in (("", False), ("_tile", True)):
+            cands["gate_up" + n] = lambda c, t=t: ops.moe_grouped_gemm(
+                x, wgu[c], routes[c], out=hs[c], tiles=t)
+            cands["down" + n] = lambda c, t=t: ops.moe_grouped_gemm(
+                hs[c], wd[c], routes[c], down=True, out=ys[c], tiles=t)
+        graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
+                  for n, f in cands.items()}
+        samples = {n: [] for n in cands}
+        reps = 10 if T <= 2048 else 3                 # the 32-row kernel takes tens of ms up there
+        for _ in range(7):                            # interleaved: same box, same minute
+            for n in cands:
+                samples[n].append(bm._timed(torch, graphs[n], reps) / copies)
+        P = T * k
+        flop = {"moe": 6 * P * H * I, "gate_up": 4 * P * H * I, "down": 2 * P * H * I}
+        row = {"T": T, "mean_rows_per_expert": round(P / E, 2),
+               "hit_experts_per_layer": round(hit, 2), "copies": copies,
+               "expert_MB_touched": round(touched / 1e6, 1),
+               "max_abs_diff_vs_loop": {n: round(v, 4) for n, v in err.items()},
+               "max_abs_loop": round(ref.abs().max().item(), 3)}
+        for n in cands:
+            us = statistics.median(samples[n])
+            row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
+                      "max_us": round(max(samples[n]), 2),
+                      "TFLOPs": round(flop[n.replace("_tile", "").replace("loop", "moe")]
+                                      / us / 1e6, 1)}
+        for n in ("moe", "gate_up", "down"):
+            t, s = row[n + "_tile"], row[n]
+            t["vs_" + n] = round(t["us"] / s["us"], 3)
+            # the min-max ranges of the rounds do not overlap
+            t["separated"] = bool(t["max_us"] < s["min_us"] or s["max_us"] < t["min_us"])
+        row["moe_tile"]["vs_loop"] = round(row["moe_tile"]["us"] / row["loop"]["us"], 3)
+        row["moe"]["vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        print(f"{name:14s} T={T:5d} rows/expert {P / E:7.1f}  moe {row['moe']['us']:10.1f} us  "
+              f"moe_tile {row['moe_tile']['us']:10.1f} us ({row['moe_tile']['TFLOPs']:.0f} TF, "
+              f"x{row['moe_tile']['vs_moe']:.3f} of moe, x{row['moe_tile']['vs_loop']:.3f} of loop)"
+              f"  loop {row['loop']['us']:10.1f} us  gate_up {row['gate_up']['us']:.1f} -> "
+              f"{row['gate_up_tile']['us']:.1f}  down {row['down']['us']:.1f} -> "
+              f"{row['down_tile']['us']:.1f}", flush=True)
+        bm._save(a, "moe_tile.json", res)
+        del graphs
+        torch.cuda.empty_cache()
+    del wgu, wd
+    torch.cuda.empty_cache()
+
+
 def bench_shared(torch, ops, F, name, rows, res, a):
     """The Qwen2-MoE block with its shared expert, fused against unfused (module docstring)."""
     from distributed_llm_inference.config import PRESETS
@@ -289,13 +398,19 @@ def main():
                     help="fp8 expert weights against bf16 (moe_fp8.json) instead of moe against loop")
     ap.add_argument("--fp4", action="store_true",
                     help="MXFP4 and fp8 expert weights against bf16 (moe_fp4.json)")
+    ap.add_argument("--tile", action="store_true",
+                    help="the tile GEMM for many rows per expert against the weight-streaming "
+                         "kernel and the loop (moe_tile.json)")
     ap.add_argument("--note", default="", help="free text kept in the result file (--fp8 / --fp4)")
     a = ap.parse_args()
-    if a.shared and (a.fp8 or a.fp4):
-        ap.error("--shared measures bf16 weights: not with --fp8 / --fp4")
+    if (a.shared or a.tile) and (a.fp8 or a.fp4):
+        ap.error("--shared / --tile measure bf16 weights: not with --fp8 / --fp4")
+    if a.shared and a.tile:
+        ap.error("--shared or --tile, not both")
     a.models = a.models or ("qwen1.5-moe-a2.7b,qwen2-57b-a14b" if a.shared
                             else "qwen3-30b-a3b,mixtral-8x7b")
-    a.rows = a.rows or ("1,4,32,512" if a.shared else "1,8,64,512")
+    a.rows = a.rows or ("1,4,32,512" if a.shared else "64,512,2048,8192" if a.tile
+                        else "1,8,64,512")
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
     import torch.nn.functional as F
@@ -335,13 +450,30 @@ def main():
             "unfused": "the same shared expert and routed experts with a separate H -> 1 "
                        "product, sigmoid * mul and add as torch ops",
             "shared_expert": "the shared expert's dense MLP alone (part of both)"}
-    if (a.fp8 or a.fp4 or a.shared) and a.note:
+    if a.tile:
+        res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays, 3 "
+                       "past T = 2048, over `copies` layers); TFLOPs = 6 T k H I (gate_up: 4, "
+                       "down: 2) / time; vs_* = time ratio; separated = the min-max ranges of "
+                       "the rounds of the two kernels do not overlap")
+        res["candidates"] = {
+            "moe": "moe_route, both grouped products on the weight-streaming kernel (32-row "
+                   "tiles), moe_combine",
+            "moe_tile": "the same launches with both products on the MFMA tile GEMM (128-row "
+                        "tiles, moe_tile.hip)",
+            "loop": "per hit expert: index_select, F.linear, swiglu, F.linear, index_add_ "
+                    "(fp32); routing on the host, not timed",
+            "gate_up / down, gate_up_tile / down_tile": "the two products alone, on either kernel"}
+    if (a.fp8 or a.fp4 or a.shared or a.tile) and a.note:
         res["note"] = a.note
     with torch.no_grad():
         for name in a.models.split(","):
             if a.shared:
                 bench_shared(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
                              res, a)
+                continue
+            if a.tile:
+                bench_tile(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
+                           res, a)
                 continue
             bench_model(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")], res, a)
     return 0
