@@ -40,6 +40,15 @@ __device__ __forceinline__ T wave_reduce_max(T v) {
   return v;
 }
 
+// the LDS / global address spaces, as the LDS-DMA builtins want their pointers
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) void gbl_void;
+
+// 16 bytes per lane global -> LDS (LDS-DMA): the wave's 64 lanes fill 1 KB at `lds_wave_base`
+__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)lds_wave_base, 16, 0, 0);
+}
+
 // store; WT: device-scope write-through (sc1), so the value is visible to every XCD once the
 // store completes (no L2 write-back before a grid barrier / arrival counter)
 template <bool WT, typename T>
@@ -312,6 +321,16 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(uint2 v) {
   o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1];
   o[4] = c[0]; o[5] = c[1]; o[6] = d[0]; o[7] = d[1];
   return o;
+}
+
+// one dword = 8 e2m1 nibbles (element 2 b, 2 b + 1 in byte b) -> 8 bf16, scaled by s (exact for
+// s = 2^(e8m0 byte - 127): v_cvt_scalef32_pk_bf16_fp4 widens a byte to packed bf16)
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(unsigned d, float s) {
+  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0);
+  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1);
+  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2);
+  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
 __device__ __forceinline__ uint8_t f32_to_fp8(float x) {

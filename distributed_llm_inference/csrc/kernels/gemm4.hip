@@ -78,8 +78,6 @@ struct G4Mx {
   int nb;                // ceil(M / 64)
 };
 
-typedef __attribute__((address_space(3))) void g4_lds_t;
-
 template <bool V>
 struct G4B { static constexpr bool value = V; };
 
@@ -368,12 +366,12 @@ gemm4_kernel(const void* __restrict__ Av, const void* __restrict__ Bv, void* __r
       const int koff = __builtin_amdgcn_readfirstlane((kt0 + t) * 128);
       if (j < 8) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsA, (g4_lds_t*)(smem + s * kG4Stage + (4 * j + w) * 1024), 16, voA[j], koff, 0,
+            rsA, (lds_void*)(smem + s * kG4Stage + (4 * j + w) * 1024), 16, voA[j], koff, 0,
             GEMM4_A_AUX);
       } else {
         const int jb = j - 8;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsB, (g4_lds_t*)(smem + s * kG4Stage + 32768 + (4 * jb + w) * 1024), 16, voB,
+            rsB, (lds_void*)(smem + s * kG4Stage + 32768 + (4 * jb + w) * 1024), 16, voB,
             __builtin_amdgcn_readfirstlane(koff + jb * 32 * Kb), 0, kBAux);
       }
     };

@@ -61,17 +61,13 @@ constexpr int kScLds = kMaxKt * 256;            // [k-tile][256 tile rows] bytes
 
 enum Epilogue { kStoreBf16 = 0, kStoreF32 = 1, kSwiGLU = 2 };
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void gbl_void_t;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void dma16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-// non-temporal (cache policy NT): the weight stream, read by at most two M-tiles
+// glds16 (common.h) with the non-temporal cache policy (NT): the weight stream, read by at most
+// two M-tiles
 __device__ __forceinline__ void dma16_nt(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 2);
+  __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)lds_wave_base, 16, 0, 2);
 }
 
 __device__ __forceinline__ void barrier() {
@@ -160,13 +156,13 @@ gemm_fp4_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ a_sc,
     if (which < 2) {
       char* dst = buf + which * kHalfA + wave * 1024;
 #pragma unroll
-      for (int j = 0; j < 2; ++j) dma16(srcA[which][j] + (size_t)t * 128, dst + j * 8192);
+      for (int j = 0; j < 2; ++j) glds16(srcA[which][j] + (size_t)t * 128, dst + j * 8192);
     } else {
       char* dst = buf + 2 * kHalfA + (which - 2) * kHalfW + wave * 1024;
       if (NT)
         dma16_nt(srcW[which - 2] + (size_t)t * 64, dst);
       else
-        dma16(srcW[which - 2] + (size_t)t * 64, dst);
+        glds16(srcW[which - 2] + (size_t)t * 64, dst);
     }
   };
   // weight scales: every wave stages the k-tile's scale dwords of its own 64 weight rows (lane l:
@@ -174,8 +170,8 @@ gemm_fp4_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ a_sc,
   // only reader of that slot (byte g of rows 32 h + 16 j + fr)
   const uint8_t* srcS = w_sc + (size_t)(n0 + wc * 64 + lane) * Ks + (size_t)kt0 * 4;
   auto stage_ws = [&](int t) {
-    __builtin_amdgcn_global_load_lds((gbl_void_t*)(srcS + (size_t)t * 4),
-                                     (lds_void_t*)(smem + kLds + (t & 1) * kWsBuf + wave * 256), 4,
+    __builtin_amdgcn_global_load_lds((gbl_void*)(srcS + (size_t)t * 4),
+                                     (lds_void*)(smem + kLds + (t & 1) * kWsBuf + wave * 256), 4,
                                      0, 0);
   };
 

@@ -67,16 +67,9 @@ enum Epilogue { kStoreBf16 = 0, kStoreF32 = 1, kSwiGLU = 2, kSwiGLUMx = 3, kStor
 // stream-K workspace header: flags [0, kSkMaxWgs), error counter at kSkErrWord, slabs after
 constexpr int kSkMaxWgs = 1020, kSkErrWord = 1023, kSkHeaderFloats = 1024;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void gbl_void_t;
-
-__device__ __forceinline__ void dma16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
-// non-temporal (cache policy NT): data streamed through once
+// glds16 (common.h) with the non-temporal cache policy (NT): data streamed through once
 __device__ __forceinline__ void dma16_nt(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 2);
+  __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)lds_wave_base, 16, 0, 2);
 }
 
 __device__ __forceinline__ void barrier() {
@@ -309,7 +302,7 @@ gemm_tile_kernel(const void* __restrict__ Av, const void* __restrict__ Bv, void*
         if ((VAR & 1) != 0 && which >= 2)
           dma16_nt(src + koff, dst + j * 8192);
         else
-          dma16(src + koff, dst + j * 8192);
+          glds16(src + koff, dst + j * 8192);
       }
     };
 

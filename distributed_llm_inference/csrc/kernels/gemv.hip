@@ -521,13 +521,7 @@ __global__ void __launch_bounds__(256) dequant_mxfp4_kernel(const uint8_t* __res
     const float s = __uint_as_float((unsigned)bscale[i] << 23);
     bf16x8* o = reinterpret_cast<bf16x8*>(out) + i * 4;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 0);
-      const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 1);
-      const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 2);
-      const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[d], s, 3);
-      o[d] = bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-    }
+    for (int d = 0; d < 4; ++d) o[d] = fp4x8_to_bf16x8(w[d], s);
   }
 }
 

@@ -19,13 +19,12 @@
 //     expert's range is cut into tiles of <= 32 rows; at most min(E, P) + P / 32 tiles exist.
 //     Ids are clamped into [0, E), so the counts always sum to P and nothing is written outside
 //     the tables.
-//   * moe_grouped_gemm.  gemm_fp8_small.hip's structure on bf16 weights: the weight is the MFMA A
-//     operand of v_mfma_f32_16x16x32_bf16 (lane (r, g) holds W[n0 + r][128 t + 32 g + 8 i + j] for
-//     MFMA i of k-step t: four non-temporal 16-byte loads per A tile and step), 32 weight rows per
-//     workgroup, the 8 waves split K, each wave stages the x of its own k-step by LDS-DMA in a
-//     private double buffer (swizzle on the source address) and the partials are added in wave
-//     order in LDS.  Grid (N / 32, tile capacity); workgroup (nb, tile) multiplies the <= 32 rows
-//     of its tile with rows 32 nb .. 32 nb + 31 of its tile's expert.  A tile index >= n_tiles
+//   * moe_grouped_gemm.  The small kernels' product, wstream_core.h's, on the experts' weights
+//     (the operand layouts of the three formats, x through LDS, the K split over the 8 waves and
+//     the load pipeline are described there).  Grid (N / 32, tile capacity); workgroup (nb, tile)
+//     multiplies the <= 32 rows of its tile with rows 32 nb .. 32 nb + 31 of its tile's expert:
+//     the weight rows are loaded as they are (N % 32 == 0), the x rows through the tile's table
+//     (below; image rows past the tile's count repeat its last row).  A tile index >= n_tiles
 //     returns before any DMA or barrier.  1-16 rows use one MFMA B tile, 17-32 two (a
 //     workgroup-uniform branch on the table's row count, not a host dispatch).  An expert with
 //     more than 32 rows is read once per tile (through L2 / Infinity Cache when its tiles run
@@ -39,24 +38,17 @@
 //     Every table value is clamped before it forms an address (expert into [0, E), rows into
 //     [1, 32], start + rows <= P, pair < P hence token < T): a garbage table cannot leave the
 //     buffers.
-//     fp8 weights (WF = kMoeFp8: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32): the same kernel
-//     with gemm_fp8_small.hip's A operand -- lane (r, g) loads the 32 bytes
-//     W8[n0 + 16 a + r][128 t + 32 g .. + 31] as two non-temporal 16-byte loads per A tile and
-//     step, and dwords 2 i, 2 i + 1, widened e4m3 -> bf16 in registers (exact), are its A fragment
-//     of MFMA i: the k order, the wave's steps and the order of the MFMAs are the bf16 variant's.
-//     The activations are never quantised; the scale of weight row n of expert e,
-//     w_scale[e N + n], multiplies the fp32 accumulator after the K-split sum (gate and up each
-//     by their own row's scale before their bf16 rounding).
+//     bf16 weights (WF = kMoeBf16): W [E, N, K].
+//     fp8 weights (WF = kMoeFp8: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32): the k order, the
+//     wave's steps and the order of the MFMAs are the bf16 variant's.  The activations are never
+//     quantised; the scale of weight row n of expert e, w_scale[e N + n], multiplies the fp32
+//     accumulator after the K-split sum (gate and up each by their own row's scale before their
+//     bf16 rounding).
 //     MXFP4 weights (WF = kMoeFp4: W4 [E, N, K / 2] bytes, element 2 j in the low nibble of byte
-//     j, bscale [E, N, K / 32] e8m0 bytes): the same kernel with gemm_fp4_small.hip's A operand --
-//     lane (r, g) loads the 16 bytes W4[n0 + 16 a + r][64 t + 16 g .. + 15] = W[..][128 t + 32 g
-//     .. + 31] as one non-temporal 16-byte load per A tile and step, exactly one scale block, and
-//     the block's byte bscale[n0 + 16 a + r][4 t + g]; dword i, widened e2m1 -> bf16 in registers
-//     with the block's 2^(byte - 127) (v_cvt_scalef32_pk_bf16_fp4, exact), is its A fragment of
-//     MFMA i: again the k order, the wave's steps and the order of the MFMAs are the bf16
-//     variant's, so the result is the bf16 kernel's on the dequantised weights bit for bit.  The
-//     scale is spent in the widening: nothing is left for the epilogue, and the activations are
-//     never quantised.
+//     j, bscale [E, N, K / 32] e8m0 bytes): again the k order, the wave's steps and the order of
+//     the MFMAs are the bf16 variant's, so the result is the bf16 kernel's on the dequantised
+//     weights bit for bit.  The scale is spent in the widening: nothing is left for the epilogue,
+//     and the activations are never quantised.
 //   * moe_combine.  out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order.
 //
 // Shared expert (Qwen2-MoE): every token of a sparse layer also runs one dense SwiGLU expert, on
@@ -72,7 +64,7 @@
 //   * moe_combine<true>: out[t] = bf16(sum_slot w[t, slot] * y[t k + slot] + shared_w[t] * s[t]),
 //     fp32, the slots in order, then the shared term, then the one rounding; the vector width,
 //     the guard and the launch shape are moe_combine<false>'s.
-#include "kernels.h"
+#include "wstream_core.h"
 
 namespace dli {
 
@@ -222,47 +214,16 @@ moe_group_kernel(const int* __restrict__ ids, int* __restrict__ expert_count,
 }
 
 // ------------------------------------------------------------------------------------- grouped GEMM
-constexpr int kWaves = 8;              // K-split ways = waves per workgroup
-constexpr int kThreads = kWaves * 64;
-constexpr int kRowsWg = 32;            // weight rows per workgroup: two 16-row A tiles
 constexpr int kTileRows = 32;          // activation rows per tile: two 16-column B tiles
 
 enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
-enum MoeWf { kMoeBf16 = 0, kMoeFp8 = 1, kMoeFp4 = 2 };
+enum MoeWf { kMoeBf16 = kWsBf16, kMoeFp8 = kWsFp8, kMoeFp4 = kWsFp4 };
 
 // k-steps of weight loads in flight per lane: 8 (bf16) / 4 (fp8) 16-byte loads per step, 16
 // loads in flight either way (fp8 with 2 measured 0-4 % slower: docs/kernels.md); fp4 has 2
 // 16-byte loads and 2 scale bytes per step: 4 + 4 in flight with 2, which measured 0-7 % faster
 // than 4 and 8 at 1-16 rows and 4-5 % slower than 4 at Mixtral's 128 / 512 rows (docs/kernels.md)
 template <int WF> constexpr int kUnrollOf = WF == kMoeFp8 ? 4 : 2;
-static_assert(kUnrollOf<kMoeBf16> % 2 == 0 && kUnrollOf<kMoeFp8> % 2 == 0 &&
-                  kUnrollOf<kMoeFp4> % 2 == 0,
-              "a group starts on x buffer 0");
-
-typedef unsigned u32x4m __attribute__((ext_vector_type(4)));   // nontemporal-loadable 16 B
-
-typedef __attribute__((address_space(3))) void lds_void_m;
-typedef __attribute__((address_space(1))) void gbl_void_m;
-
-// 16 bytes per lane global -> LDS (LDS-DMA): the wave's 64 lanes fill 1 KB at `lds_wave_base`
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_m*)g, (lds_void_m*)lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// the 16-byte slot of chunk ch of x row c in the staged image is ch ^ swz(c)
-__device__ __forceinline__ int swz(int c) { return c ^ ((c & 4) << 1); }
-
-// one dword = 8 e2m1 nibbles (element 2 b, 2 b + 1 in byte b) -> 8 bf16, scaled by s (exact)
-__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(unsigned d, float s) {
-  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0);
-  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1);
-  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2);
-  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3);
-  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
 
 __device__ __forceinline__ int clamp_pair(int p, int P) { return min(max(p, 0), P - 1); }
 
@@ -276,165 +237,23 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
                                          const void* __restrict__ wscale, bf16* __restrict__ out,
                                          const int* __restrict__ pairs, int start, int rows,
                                          int nb, int topk, int P, int N, int K) {
-  constexpr int kWB = WF == kMoeBf16 ? 2 : 1;   // bytes per weight (kMoeFp4: half a byte, below)
-  constexpr int kWL = WF == kMoeFp4 ? 1 : 2 * kWB;   // 16-byte loads per A tile and k-step
-  constexpr int kStepB = 16 * 4 * kWL;         // bytes of a weight row per k-step: 4 lanes' loads
-  constexpr int kUnroll = kUnrollOf<WF>;
-  constexpr int kXBuf = MT * 16 * 256;   // one k-step of x: 16 MT rows x 128 bf16
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
-  const int n0 = nb * kRowsWg;
-  const int kt = K >> 7;
-  char* xw = smem + wave * (2 * kXBuf);   // this wave's two x buffers; nobody else touches them
+  const int n0 = nb * kWsRowsWg;
 
-  // this lane's weight rows (A tiles 0 / 1; N % 32 == 0: both whole) at its 32-k block of step 0
-  // (kMoeFp4: a row is K / 2 bytes, and the lane's scale byte of step 0 is block g of its row)
-  const char* wp[2];
-  const uint8_t* sp[2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const size_t n = (size_t)(n0 + 16 * a + r);
-    if constexpr (WF == kMoeFp4) {
-      wp[a] = W + n * (size_t)(K >> 1) + 16 * g;
-      sp[a] = static_cast<const uint8_t*>(wscale) + n * (size_t)(K >> 5) + g;
-    } else {
-      wp[a] = W + (n * K + 32 * g) * kWB;
-      sp[a] = nullptr;
-    }
-  }
-  // x staging: DMA instruction q fills image rows 4 q .. 4 q + 3 (lane l: row 4 q + (l >> 4),
-  // slot l & 15) with whole 256-byte row pieces; the slot permutation is on the source address.
-  // Image rows past `rows` repeat the tile's last row.
-  const bf16* xsrc[4 * MT];
-#pragma unroll
-  for (int q = 0; q < 4 * MT; ++q) {
-    const int row = 4 * q + g;
-    const int tr = min(row, rows - 1);
-    size_t src;
-    if constexpr (EPI == kMoeGateUp) src = (size_t)(clamp_pair(pairs[tr], P) / topk);   // token
-    else src = (size_t)(start + tr);                                                    // h row
-    xsrc[q] = x + src * K + ((r ^ swz(row & 15)) << 3);
-  }
-  // ... and the fragment reads: B fragment i of lane (c = r, g) is chunk 4 g + i of row 16 b + c
-  int xoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) xoff[i] = r * 256 + (((4 * g + i) ^ swz(r)) << 4);
-
+  // N % 32 == 0: both A tiles are whole.  Image rows past `rows` repeat the tile's last row.
   f32x4 acc[2][MT];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // k-step t < kt: every address below stays inside its row (K % 128 == 0)
-  // kMoeFp4: the scale bytes are vector memory loads too, issued here with the weight loads,
-  // i.e. before the next stage_x -- so "all but the 4 MT newest" below still covers them
-  auto load_w = [&](int t, u32x4m (&wv)[2][kWL], unsigned (&sc)[2]) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-#pragma unroll
-      for (int i = 0; i < kWL; ++i)
-        wv[a][i] = __builtin_nontemporal_load(
-            reinterpret_cast<const u32x4m*>(wp[a] + (size_t)t * kStepB + 16 * i));
-      if constexpr (WF == kMoeFp4) sc[a] = sp[a][(size_t)t * 4];
-    }
-  };
-  auto stage_x = [&](int t, int buf) {
-#pragma unroll
-    for (int q = 0; q < 4 * MT; ++q)
-      glds16(xsrc[q] + (size_t)t * 128, xw + buf * kXBuf + q * 1024);
-  };
-  auto step = [&](int buf, const u32x4m (&wv)[2][kWL], const unsigned (&sc)[2]) {
-    bf16x8 xb[MT][4];
-#pragma unroll
-    for (int b = 0; b < MT; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        xb[b][i] = *reinterpret_cast<const bf16x8*>(xw + buf * kXBuf + b * 4096 + xoff[i]);
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      float s = 0.f;   // kMoeFp4: 2^(byte - 127), byte in [1, 254]
-      if constexpr (WF == kMoeFp4) s = __uint_as_float(sc[a] << 23);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        bf16x8 wf;
-        if constexpr (WF == kMoeFp4)   // dword i of the lane's 4: exact widening
-          wf = fp4x8_to_bf16x8(wv[a][0][i], s);
-        else if constexpr (WF == kMoeFp8)   // dwords 2 i, 2 i + 1 of the lane's 8: exact widening
-          wf = fp8x8_to_bf16x8(uint2{wv[a][i >> 1][2 * (i & 1)], wv[a][i >> 1][2 * (i & 1) + 1]});
-        else
-          wf = __builtin_bit_cast(bf16x8, wv[a][i]);
-#pragma unroll
-        for (int b = 0; b < MT; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb[b][i], acc[a][b], 0, 0, 0);
-      }
-    }
-  };
-
-  // This wave's steps are t = wave + i kWaves, i < nsteps.  On entering a group of kUnroll steps
-  // the x of its first step is the only memory operation in flight; the group's weight loads
-  // follow it, and every step first sends the next step's x into the other buffer, then waits
-  // for all but those 4 MT newest operations (vmcnt counts in issue order).
-  const int nsteps = wave < kt ? (kt - wave + kWaves - 1) / kWaves : 0;
-  if (nsteps > 0) stage_x(wave, 0);
-  int i = 0;
-  for (; i + kUnroll <= nsteps; i += kUnroll) {   // whole groups; kUnroll is even: buffer u & 1
-    u32x4m wv[kUnroll][2][kWL];
-    unsigned sc[kUnroll][2];
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) load_w(wave + (i + u) * kWaves, wv[u], sc[u]);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      if (u + 1 < kUnroll || i + kUnroll < nsteps) {
-        stage_x(wave + (i + u + 1) * kWaves, (u + 1) & 1);
-        wait_vm<4 * MT>();
-      } else {
-        wait_vm<0>();
-      }
-      step(u & 1, wv[u], sc[u]);
-      asm volatile("" ::: "memory");   // the next DMA into this buffer stays behind its reads
-    }
-  }
-  for (; i < nsteps; ++i) {   // fewer than kUnroll steps left
-    u32x4m wv[2][kWL];
-    unsigned sc[2];
-    load_w(wave + i * kWaves, wv, sc);
-    asm volatile("" ::: "memory");
-    if (i + 1 < nsteps) {
-      stage_x(wave + (i + 1) * kWaves, (i + 1) & 1);
-      wait_vm<4 * MT>();
-    } else {
-      wait_vm<0>();
-    }
-    step(i & 1, wv, sc);
-    asm volatile("" ::: "memory");
-  }
-
-  // ---- K-split sum: waves 1.. park their partials, wave 0 adds them in wave order ----
-  // (into its own x buffers: every DMA into them has landed and been read)
-  if (wave > 0) {
-    float* red = reinterpret_cast<float*>(xw);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < MT; ++b)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[((a * MT + b) * 4 + e) * 64 + lane] = acc[a][b][e];
-  }
-  __syncthreads();
-  if (wave > 0) return;
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) {
-    const float* red = reinterpret_cast<const float*>(smem + w * (2 * kXBuf));
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < MT; ++b)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[a][b][e] += red[((a * MT + b) * 4 + e) * 64 + lane];
-  }
+  if (!ws_accumulate<MT, WF, kUnrollOf<WF>>(
+          smem, x, W, static_cast<const uint8_t*>(wscale), n0, K, [](int n) { return n; },
+          [&](int row) {
+            const int tr = min(row, rows - 1);
+            if constexpr (EPI == kMoeGateUp)
+              return (size_t)(clamp_pair(pairs[tr], P) / topk);   // token
+            else
+              return (size_t)(start + tr);   // h row
+          },
+          acc))
+    return;
 
   // ---- epilogue: acc[a][b][e] = y[m = 16 b + r][n = n0 + 16 a + 4 g + e] ----
   if constexpr (WF == kMoeFp8) {   // the scales of the lane's four weight rows per A tile
@@ -482,14 +301,14 @@ __device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
 }
 
 template <int EPI, int WF>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kWsThreads)
 moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
                         const void* __restrict__ wscale, bf16* __restrict__ out,
                         const int* __restrict__ sorted_pairs,
                         const int* __restrict__ tile_expert, const int* __restrict__ tile_start,
                         const int* __restrict__ tile_rows, const int* __restrict__ n_tiles,
                         int E, int topk, int P, int N, int K) {
-  __shared__ __attribute__((aligned(1024))) char smem[kWaves * 2 * (kTileRows * 256)];
+  __shared__ __attribute__((aligned(1024))) char smem[kWsSmem<kTileRows / 16>];
   const int tile = blockIdx.y, nb = blockIdx.x;
   if (tile >= n_tiles[0]) return;   // before any DMA or barrier
   const int e = min(max(tile_expert[tile], 0), E - 1);
@@ -592,14 +411,14 @@ int launch_grouped(bf16* out, const bf16* x, const void* W, const void* wscale,
   if (cap <= 0 || cap > 65535 || (long)T * k > (1L << 30)) return -3;
   if (out == nullptr || x == nullptr || W == nullptr) return -5;
   if (WF != kMoeBf16 && wscale == nullptr) return -5;
-  const dim3 grid(N / kRowsWg, cap);
+  const dim3 grid(N / kWsRowsWg, cap);
   const int P = T * k;
   if (epilogue == kMoeGateUp)
-    moe_grouped_gemm_kernel<kMoeGateUp, WF><<<grid, kThreads, 0, stream>>>(
+    moe_grouped_gemm_kernel<kMoeGateUp, WF><<<grid, kWsThreads, 0, stream>>>(
         x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
         K);
   else if (epilogue == kMoeDown)
-    moe_grouped_gemm_kernel<kMoeDown, WF><<<grid, kThreads, 0, stream>>>(
+    moe_grouped_gemm_kernel<kMoeDown, WF><<<grid, kWsThreads, 0, stream>>>(
         x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
         K);
   else

@@ -49,14 +49,6 @@ constexpr int kBuf = 2 * kOp;     // weight tile | activation tile
 
 enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
 
-typedef __attribute__((address_space(3))) void lds_void_mt;
-typedef __attribute__((address_space(1))) void gbl_void_mt;
-
-// 16 bytes per lane global -> LDS (LDS-DMA): the wave's 64 lanes fill 1 KB at `lds_wave_base`
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_mt*)g, (lds_void_mt*)lds_wave_base, 16, 0, 0);
-}
-
 template <int EPI>
 __global__ void __launch_bounds__(kThreads, 2)
 moe_tile_gemm_kernel(const bf16* __restrict__ x, const bf16* __restrict__ W,
