@@ -709,8 +709,17 @@ class KernelPolicy:
     # routed experts on the grouped MFMA tile GEMM (csrc/kernels/moe_tile.hip: 128-row tiles, a
     # weight byte read once per 128 rows) instead of the weight-streaming kernel's 32-row tiles.
     # 0 = off, else 32..1024 (docs/kernels.md "Sparse MoE: tile GEMM" has the measured
-    # crossover); fp8 / MXFP4 experts and the CPU path ignore it
+    # crossover); the CPU path ignores it, and fp8 / MXFP4 experts follow moe_tile_rows_q instead
     moe_tile_rows: int = 0
+    # sparse MoE, fp8 / MXFP4 experts: the same switch for quantised experts (moe_tile.hip's fp8
+    # and MXFP4 instantiations: the quantised bytes staged in LDS and widened to bf16 at
+    # fragment-read time).  A knob of its own: the weight-streaming kernel reads a half or a
+    # quarter of the bytes here, so the crossover is not the bf16 one.  0 = off, else 32..1024.
+    # Suggested where prefill matters: 32, the smallest mean rows per expert at which both
+    # Qwen3-30B-A3B and Mixtral-8x7B shapes were measured, and faster than the weight-streaming
+    # kernel on both, in both formats (docs/kernels.md "Sparse MoE: tile GEMM, quantised
+    # experts": 3.6-4.9x at 2048-8192 rows for fp8, 3.1-4.0x for MXFP4)
+    moe_tile_rows_q: int = 0
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 
@@ -721,6 +730,8 @@ class KernelPolicy:
             raise ValueError(f"fp8_small_m={self.fp8_small_m}: 0 (off) or 3..32")
         if self.moe_tile_rows != 0 and not 32 <= self.moe_tile_rows <= 1024:
             raise ValueError(f"moe_tile_rows={self.moe_tile_rows}: 0 (off) or 32..1024")
+        if self.moe_tile_rows_q != 0 and not 32 <= self.moe_tile_rows_q <= 1024:
+            raise ValueError(f"moe_tile_rows_q={self.moe_tile_rows_q}: 0 (off) or 32..1024")
         if self.gemm4_decode_sched not in (4, 6, 8, 9):
             raise ValueError(f"gemm4_decode_sched={self.gemm4_decode_sched}: 4, 6, 8 or 9")
         sel = self.fp8_gemm4

@@ -1151,6 +1151,34 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
                                         (int)epilogue, cur_stream()), "moe_grouped_gemm");
 }
 
+// the tile kernel's (moe_tile.hip) shape and device checks, common to its three weight formats:
+// K is the logical reduction length (twice w's last dimension for MXFP4 nibbles); returns E
+int64_t check_moe_tile(const char* what, const Tensor& out, const Tensor& x, const Tensor& w,
+                       const Tensor& sorted_pairs, const Tensor& expert_count,
+                       const Tensor& expert_offset, int64_t T, int64_t k, int64_t epilogue,
+                       int64_t K) {
+  TORCH_CHECK(epilogue == 0 || epilogue == 1, what, ": epilogue 0 (gate|up) or 1 (down)");
+  const int64_t E = w.size(0), N = w.size(1);
+  TORCH_CHECK(T >= 1 && T <= (1 << 24) && E >= 1 && E <= 256 && k >= 1 && k <= 8,
+              what, ": 1 <= T <= 2^24, E <= 256, k <= 8");
+  const int64_t P = T * k;
+  TORCH_CHECK(dli::moe_tile_gemm_capacity((int)T, (int)E, (int)k) <= 65535,
+              what, ": more than 65535 tiles (T * k too large for one launch)");
+  TORCH_CHECK(sorted_pairs.numel() == P && expert_count.numel() == E &&
+                  expert_offset.numel() == E + 1,
+              what, ": sorted_pairs [T k], expert_count [E], expert_offset [E + 1]");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= (1 << 24), what, ": needs K % 64 == 0");
+  TORCH_CHECK(N >= 128 && N % 128 == 0 && N <= (1 << 24), what, ": needs N % 128 == 0");
+  TORCH_CHECK(x.size(1) == K && x.size(0) >= (epilogue == 0 ? T : P),
+              what, ": x [T, K] (gate|up) or [>= T k, K] (down)");
+  TORCH_CHECK(out.size(0) >= P && out.size(1) == (epilogue == 0 ? N / 2 : N),
+              what, ": out [>= T k, N / 2] (gate|up) or [>= T k, N] (down)");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
+                  sorted_pairs.device() == x.device() && expert_count.device() == x.device() &&
+                  expert_offset.device() == x.device(), what, ": one device");
+  return E;
+}
+
 // moe_grouped_gemm's products for bf16 W on the tile kernel (moe_tile.hip): 128-row tiles derived
 // in the kernel from expert_count [E] / expert_offset [E + 1]; N % 128 == 0, K % 64 == 0
 void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor expert_count,
@@ -1164,30 +1192,70 @@ void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor e
               "moe_grouped_gemm)");
   TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
               "moe_tile_gemm: out / x 2-D, w [E, N, K]");
-  TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_tile_gemm: epilogue 0 (gate|up) or 1 (down)");
-  const int64_t E = w.size(0), N = w.size(1), K = w.size(2);
-  TORCH_CHECK(T >= 1 && T <= (1 << 24) && E >= 1 && E <= 256 && k >= 1 && k <= 8,
-              "moe_tile_gemm: 1 <= T <= 2^24, E <= 256, k <= 8");
-  const int64_t P = T * k;
-  TORCH_CHECK(dli::moe_tile_gemm_capacity((int)T, (int)E, (int)k) <= 65535,
-              "moe_tile_gemm: more than 65535 tiles (T * k too large for one launch)");
-  TORCH_CHECK(sorted_pairs.numel() == P && expert_count.numel() == E &&
-                  expert_offset.numel() == E + 1,
-              "moe_tile_gemm: sorted_pairs [T k], expert_count [E], expert_offset [E + 1]");
-  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= (1 << 24), "moe_tile_gemm: needs K % 64 == 0");
-  TORCH_CHECK(N >= 128 && N % 128 == 0 && N <= (1 << 24), "moe_tile_gemm: needs N % 128 == 0");
-  TORCH_CHECK(x.size(1) == K && x.size(0) >= (epilogue == 0 ? T : P),
-              "moe_tile_gemm: x [T, K] (gate|up) or [>= T k, K] (down)");
-  TORCH_CHECK(out.size(0) >= P && out.size(1) == (epilogue == 0 ? N / 2 : N),
-              "moe_tile_gemm: out [>= T k, N / 2] (gate|up) or [>= T k, N] (down)");
-  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
-                  sorted_pairs.device() == x.device() && expert_count.device() == x.device() &&
-                  expert_offset.device() == x.device(), "moe_tile_gemm: one device");
+  const int64_t N = w.size(1), K = w.size(2);
+  const int64_t E = check_moe_tile("moe_tile_gemm", out, x, w, sorted_pairs, expert_count,
+                                   expert_offset, T, k, epilogue, K);
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   check_rc(dli::launch_moe_tile_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
                                      expert_count.data_ptr<int>(), expert_offset.data_ptr<int>(),
                                      (int)T, (int)E, (int)k, (int)N, (int)K, (int)epilogue,
                                      cur_stream()), "moe_tile_gemm");
+}
+
+// the same on fp8 experts: w8 [E, N, K] e4m3fn, w_scale [E, N] fp32 (one per weight row, applied
+// to the fp32 accumulator); the activations stay bf16
+void moe_tile_gemm_fp8(Tensor out, Tensor x, Tensor w8, Tensor w_scale, Tensor sorted_pairs,
+                       Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
+                       int64_t epilogue) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w8); CHECK_IN(w_scale);
+  CHECK_BF16(out); CHECK_BF16(x);
+  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
+  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
+  TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn && w_scale.scalar_type() == at::kFloat,
+              "moe_tile_gemm_fp8: fp8 e4m3fn expert weights with fp32 w_scale");
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w8.dim() == 3,
+              "moe_tile_gemm_fp8: out / x 2-D, w8 [E, N, K]");
+  const int64_t N = w8.size(1), K = w8.size(2);
+  const int64_t E = check_moe_tile("moe_tile_gemm_fp8", out, x, w8, sorted_pairs, expert_count,
+                                   expert_offset, T, k, epilogue, K);
+  TORCH_CHECK(w_scale.dim() == 2 && w_scale.size(0) == E && w_scale.size(1) == N &&
+                  w_scale.device() == x.device(),
+              "moe_tile_gemm_fp8: w_scale [E, N] on the weights' device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_moe_tile_gemm_fp8(
+               bp(out), bp(x), static_cast<const uint8_t*>(w8.data_ptr()),
+               w_scale.data_ptr<float>(), sorted_pairs.data_ptr<int>(),
+               expert_count.data_ptr<int>(), expert_offset.data_ptr<int>(), (int)T, (int)E,
+               (int)k, (int)N, (int)K, (int)epilogue, cur_stream()), "moe_tile_gemm_fp8");
+}
+
+// the same on MXFP4 experts: w4 uint8 [E, N, K / 2] nibbles, w_block_scale uint8 [E, N, K / 32]
+// e8m0 bytes spent in the exact widening to bf16; K % 128 == 0
+void moe_tile_gemm_fp4(Tensor out, Tensor x, Tensor w4, Tensor w_block_scale,
+                       Tensor sorted_pairs, Tensor expert_count, Tensor expert_offset, int64_t T,
+                       int64_t k, int64_t epilogue) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w4); CHECK_IN(w_block_scale);
+  CHECK_BF16(out); CHECK_BF16(x);
+  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
+  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
+  TORCH_CHECK(w4.scalar_type() == at::kByte && w_block_scale.scalar_type() == at::kByte,
+              "moe_tile_gemm_fp4: uint8 MXFP4 expert weights with uint8 w_block_scale");
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w4.dim() == 3,
+              "moe_tile_gemm_fp4: out / x 2-D, w4 [E, N, K / 2]");
+  const int64_t N = w4.size(1), K = 2 * w4.size(2);
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "moe_tile_gemm_fp4: needs K % 128 == 0");
+  const int64_t E = check_moe_tile("moe_tile_gemm_fp4", out, x, w4, sorted_pairs, expert_count,
+                                   expert_offset, T, k, epilogue, K);
+  TORCH_CHECK(w_block_scale.dim() == 3 && w_block_scale.size(0) == E &&
+                  w_block_scale.size(1) == N && w_block_scale.size(2) == K / 32 &&
+                  w_block_scale.device() == x.device(),
+              "moe_tile_gemm_fp4: w_block_scale [E, N, K / 32] on the weights' device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_moe_tile_gemm_fp4(
+               bp(out), bp(x), w4.data_ptr<uint8_t>(), w_block_scale.data_ptr<uint8_t>(),
+               sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
+               expert_offset.data_ptr<int>(), (int)T, (int)E, (int)k, (int)N, (int)K,
+               (int)epilogue, cur_stream()), "moe_tile_gemm_fp4");
 }
 
 // shared [T, H] (bf16) with shared_w [T] (fp32): the shared expert's term, added after the slots
@@ -1487,6 +1555,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"));
+  m.def("moe_tile_gemm_fp8", &moe_tile_gemm_fp8,
+        "the tile GEMM over fp8 e4m3fn experts with fp32 row scales [E, N]",
+        py::arg("out"), py::arg("x"), py::arg("w8"), py::arg("w_scale"), py::arg("sorted_pairs"),
+        py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
+        py::arg("epilogue"));
+  m.def("moe_tile_gemm_fp4", &moe_tile_gemm_fp4,
+        "the tile GEMM over MXFP4 experts [E, N, K / 2] with e8m0 block scales [E, N, K / 32]",
+        py::arg("out"), py::arg("x"), py::arg("w4"), py::arg("w_block_scale"),
+        py::arg("sorted_pairs"), py::arg("expert_count"), py::arg("expert_offset"),
+        py::arg("T"), py::arg("k"), py::arg("epilogue"));
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"), py::arg("shared") = py::none(),
         py::arg("shared_w") = py::none());

@@ -217,6 +217,20 @@ int moe_tile_gemm_capacity(int T, int E, int k);
 int launch_moe_tile_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
                          const int* expert_count, const int* expert_offset, int T, int E, int k,
                          int N, int K, int epilogue, hipStream_t stream);
+// the same tiles on quantised experts: the quantised bytes are staged in LDS and widened exactly
+// to bf16 when a fragment is read, so the MFMAs and their order are launch_moe_tile_gemm's.
+// fp8: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32 applied to the fp32 accumulator (gate and
+// up each by their own row's scale before their bf16 rounding).  MXFP4: W4 [E, N, K / 2] nibbles,
+// bscale [E, N, K / 32] e8m0 bytes spent in the widening, K % 128 == 0: the bf16 kernel's result
+// on the dequantised weights, bit for bit.  The scale pointers must not be null (-5)
+int launch_moe_tile_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
+                             const int* sorted_pairs, const int* expert_count,
+                             const int* expert_offset, int T, int E, int k, int N, int K,
+                             int epilogue, hipStream_t stream);
+int launch_moe_tile_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
+                             const int* sorted_pairs, const int* expert_count,
+                             const int* expert_offset, int T, int E, int k, int N, int K,
+                             int epilogue, hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

@@ -1432,13 +1432,17 @@ def moe_route(logits: torch.Tensor, k: int, renorm: bool,
 def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
     """Whether a sparse-MoE call of T tokens, top-k of E experts runs its routed experts on the
     grouped MFMA tile GEMM (moe_tile.hip) instead of the weight-streaming kernel (moe.hip):
-    ``KernelPolicy.moe_tile_rows`` is set, the expert weights are bf16 (``weight_format``:
-    "bf16", "fp8" or "mxfp4"), the call is on the GPU (``device``: the activations'), and the
-    mean rows per expert reach the threshold, ``T k >= moe_tile_rows E``.  Host-known integers
-    only: no device sync."""
-    rows = policy().moe_tile_rows
-    return bool(rows and torch.device(device).type == "cuda" and weight_format == "bf16"
-                and T * k >= rows * E)
+    the policy field of the experts' format is set -- ``KernelPolicy.moe_tile_rows`` for
+    ``weight_format`` "bf16", ``KernelPolicy.moe_tile_rows_q`` for "fp8" and "mxfp4" -- the call
+    is on the GPU (``device``: the activations'), and the mean rows per expert reach that
+    threshold, ``T k >= rows E``.  Host-known integers only: no device sync."""
+    if weight_format == "bf16":
+        rows = policy().moe_tile_rows
+    elif weight_format in ("fp8", "mxfp4"):
+        rows = policy().moe_tile_rows_q
+    else:
+        rows = 0
+    return bool(rows and torch.device(device).type == "cuda" and T * k >= rows * E)
 
 
 def _moe_weight_format(w: torch.Tensor, w_scale, w_block_scale) -> str:
@@ -1463,17 +1467,23 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     nibbles ``uint8 [E, N, K / 2]`` (:func:`quantize_expert_weights_mxfp4`), widened exactly to
     bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights.
 
-    ``tiles``: True runs the grouped MFMA tile GEMM (moe_tile.hip: bf16 weights on the GPU,
-    N % 128 == 0, K % 64 == 0; the same products, another K summation order), False the
-    weight-streaming kernel, None lets :func:`moe_uses_tiles` decide.  The CPU path ignores it."""
+    ``tiles``: True runs the grouped MFMA tile GEMM (moe_tile.hip, on the GPU: N % 128 == 0,
+    K % 64 == 0; the same products, another K summation order), False the weight-streaming
+    kernel, None lets :func:`moe_uses_tiles` decide.  bf16 weights can always be forced onto the
+    tiles; fp8 and MXFP4 weights only while ``KernelPolicy.moe_tile_rows_q`` is set (with it at 0
+    ``tiles=True`` on them is a ``ValueError``).  The quantised tile kernels widen the weights
+    exactly to bf16 and run the bf16 tile kernel's MFMAs in its order: MXFP4 gives its result on
+    the dequantised weights bit for bit, fp8 the same up to the row scale applied to the fp32
+    sum.  The CPU path ignores ``tiles``."""
     T, k = r.topk_ids.shape
     P, N = T * k, w.shape[1]
     fmt = _moe_weight_format(w, w_scale, w_block_scale)
     if tiles is None:
         tiles = moe_uses_tiles(T, k, w.shape[0], fmt, x.device)
-    elif tiles and _gpu(x) and fmt != "bf16":
+    elif tiles and _gpu(x) and fmt != "bf16" and not policy().moe_tile_rows_q:
         raise ValueError(f"moe_grouped_gemm: tiles=True needs bf16 expert weights, got {fmt} "
-                         "(quantised experts run on the weight-streaming kernel)")
+                         "(quantised experts run on the weight-streaming kernel unless "
+                         "KernelPolicy.moe_tile_rows_q is set)")
     if w_block_scale is not None or w.dtype == torch.uint8:
         if w_scale is not None:
             raise ValueError("moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both")
@@ -1501,8 +1511,16 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
                              "w_scale [E, N]")
         return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale, w_block_scale)
     if tiles:
-        native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
-                               r.expert_offset, T, k, 1 if down else 0)
+        if w_block_scale is not None:
+            native().moe_tile_gemm_fp4(out, x.contiguous(), w, w_block_scale.contiguous(),
+                                       r.sorted_pairs, r.expert_count, r.expert_offset, T, k,
+                                       1 if down else 0)
+        elif w_scale is not None:
+            native().moe_tile_gemm_fp8(out, x.contiguous(), w, w_scale, r.sorted_pairs,
+                                       r.expert_count, r.expert_offset, T, k, 1 if down else 0)
+        else:
+            native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
+                                   r.expert_offset, T, k, 1 if down else 0)
         return out
     if w_block_scale is not None:
         native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
@@ -1555,8 +1573,10 @@ def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
     SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
     expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
     with their row scales ``[E, 2I]`` / ``[E, H]``, or MXFP4 nibbles ``[E, 2I, H / 2]`` /
-    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.  bf16
-    experts with many rows each run both products on the tile GEMM (:func:`moe_uses_tiles`).
+    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.
+    Experts with many rows each run both products on the tile GEMM when their format's policy
+    field is set (:func:`moe_uses_tiles`: ``moe_tile_rows`` for bf16, ``moe_tile_rows_q`` for fp8
+    and MXFP4).
 
     Shared expert (Qwen2-MoE): ``num_experts = E`` and ``shared [T, H]`` (bf16), the shared
     expert's output, go together; ``gate_logits [T, ld]`` then hold the shared gate's logit in

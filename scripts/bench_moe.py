@@ -8,6 +8,8 @@ scripts/bench_mxfp4.py's protocol and helpers.
     python3 scripts/bench_moe.py --fp4 [...]      MXFP4 and fp8 against bf16 -> moe_fp4.json
     python3 scripts/bench_moe.py --shared [...]   Qwen2-MoE's shared expert -> moe_shared.json
     python3 scripts/bench_moe.py --tile [...]     the tile GEMM for many rows per expert -> moe_tile.json
+    python3 scripts/bench_moe.py --tile --fp8 | --fp4 [...]   the same on quantised experts
+                                                  -> moe_tile_fp8.json / moe_tile_fp4.json
 
 Per model (one layer's shapes) and per decode row count T, with random router logits:
 
@@ -55,6 +57,17 @@ products alone on either kernel (``gate_up`` / ``down`` and ``gate_up_tile`` / `
 same graphs over copies, interleaved.  Reported besides the times: achieved TFLOP/s from the
 shapes (6 T k H I per layer), the time ratios, and whether the min-max ranges of the two kernels
 are apart (``separated``).  Results: ``<out>/moe_tile.json``.
+
+``--tile --fp8`` / ``--tile --fp4`` run the same protocol on quantised experts
+(ops.quantize_expert_weights_fp8 / _mxfp4 of the random bf16 tensors; default rows 128, 512,
+2048, 8192): ``moe_tile`` (both products on the quantised tile kernels, forced with ``tiles=True``
+under ``KernelPolicy.moe_tile_rows_q``), ``moe`` (the 32-row weight-streaming kernel on the same
+quantised experts: what runs without the knob), ``loop`` (the expert loop on the dequantised bf16
+weights) and ``moe_tile_bf16`` (the bf16 tile kernel on the dequantised weights, in the same run:
+does the quantised kernel follow its bytes?), plus the two products alone on each kernel.
+``vs_bf16_tile`` is the time ratio of a quantised tile candidate to its bf16 twin and
+``weight_bytes_vs_bf16`` the ratio of the expert bytes behind it.  Results:
+``<out>/moe_tile_fp8.json`` / ``<out>/moe_tile_fp4.json``.
 """
 import argparse
 import os
@@ -309,6 +322,146 @@ def bench_tile(torch, ops, F, name, rows, res, a):
     torch.cuda.empty_cache()
 
 
+def bench_tile_q(torch, ops, F, name, rows, res, a):
+    """bench_tile's protocol on fp8 (``--fp8``) or MXFP4 (``--fp4``) experts (module docstring,
+    ``--tile --fp8`` / ``--tile --fp4``)."""
+    from distributed_llm_inference.config import PRESETS
+    spec = PRESETS[name]
+    dev = torch.device("cuda", 0)
+    H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
+                  spec.num_experts_per_tok)
+    fmt = "fp4" if a.fp4 else "fp8"
+    kw = "w_block_scale" if a.fp4 else "w_scale"
+    quantise = ops.quantize_expert_weights_mxfp4 if a.fp4 else ops.quantize_expert_weights_fp8
+    copies = 8 if E * 3 * H * I * 2 < (2 << 30) else 3   # bench_model's rule, on the bf16 bytes
+    gen = torch.Generator(device=dev).manual_seed(1)
+
+    def dequantised(q, s):
+        out = torch.empty(q.shape[0], q.shape[1], s.shape[2] * 32 if a.fp4 else q.shape[2],
+                          device=dev, dtype=torch.bfloat16)
+        for e in range(q.shape[0]):                   # one expert at a time: a small temporary
+            if a.fp4:
+                ops.dequantize_mxfp4(q[e], s[e], out=out[e])
+            else:
+                out[e] = (q[e].float() * s[e][:, None]).to(torch.bfloat16)
+        return out
+
+    # per copy: the quantised experts and their dequantised bf16 twin (the original is dropped)
+    qgu, sgu, qd, sd, wgu, wd = [], [], [], [], [], []
+    for _ in range(copies):
+        for shape, fan, qs, ss, ws in (((E, 2 * I, H), H, qgu, sgu, wgu), ((E, H, I), I, qd, sd, wd)):
+            w = torch.empty(*shape, device=dev, dtype=torch.bfloat16).normal_(0, fan ** -0.5,
+                                                                              generator=gen)
+            q, s = quantise(w)
+            del w
+            qs.append(q)
+            ss.append(s)
+            ws.append(dequantised(q, s))
+    # expert bytes per bf16 byte: fp8 adds one fp32 scale per row, MXFP4 is 17/32 byte per weight
+    byte_ratio = 17 / 64 if a.fp4 else 0.5 + (2 * I + H) * 4 / (3 * H * I * 2)
+    for T in rows:
+        x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
+        logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
+                  for _ in range(copies)]
+        routes = [ops.moe_route(lg, k, spec.norm_topk_prob) for lg in logits]
+        hit_total, loops = 0, []
+        for c in range(copies):                      # host-side routing of the baseline: not timed
+            ids, w = routes[c].topk_ids.cpu(), routes[c].topk_w.cpu()
+            per = []
+            for e in ids.unique().tolist():
+                tok, slot = (ids == e).nonzero(as_tuple=True)
+                per.append((e, tok.to(dev), w[tok, slot].to(dev)[:, None]))
+            hit_total += len(per)
+            loops.append(per)
+        hit = hit_total / copies
+        touched = hit * 3 * H * I * 2 * byte_ratio    # expert bytes one layer streams
+
+        def moe_with(tiles, bf16=False):
+            def run(c):
+                r = ops.moe_route(logits[c], k, spec.norm_topk_prob)
+                if bf16:
+                    h = ops.moe_grouped_gemm(x, wgu[c], r, tiles=tiles)
+                    y = ops.moe_grouped_gemm(h, wd[c], r, down=True, tiles=tiles)
+                else:
+                    h = ops.moe_grouped_gemm(x, qgu[c], r, tiles=tiles, **{kw: sgu[c]})
+                    y = ops.moe_grouped_gemm(h, qd[c], r, down=True, tiles=tiles, **{kw: sd[c]})
+                return ops.moe_combine(y, r.topk_w)
+            return run
+
+        def loop(c):
+            acc = torch.zeros(T, H, device=dev, dtype=torch.float32)
+            for e, tok, we in loops[c]:
+                h = ops.swiglu_interleaved(F.linear(x.index_select(0, tok), wgu[c][e]))
+                acc.index_add_(0, tok, F.linear(h, wd[c][e]).float() * we)
+            return acc.to(torch.bfloat16)
+
+        ref = loop(0).float()
+        err = {n: (f(0).float() - ref).abs().max().item()
+               for n, f in (("moe", moe_with(False)), ("moe_tile", moe_with(True)),
+                            ("moe_tile_bf16", moe_with(True, bf16=True)))}
+        hs = [ops.moe_grouped_gemm(x, qgu[c], routes[c], tiles=False, **{kw: sgu[c]})
+              for c in range(copies)]
+        ys = [ops.moe_grouped_gemm(hs[c], qd[c], routes[c], down=True, tiles=False, **{kw: sd[c]})
+              for c in range(copies)]
+        cands = {"moe": moe_with(False), "moe_tile": moe_with(True), "loop": loop,
+                 "moe_tile_bf16": moe_with(True, bf16=True)}
+        for n, t in (("", False), ("_tile", True)):
+            cands["gate_up" + n] = lambda c, t=t: ops.moe_grouped_gemm(
+                x, qgu[c], routes[c], out=hs[c], tiles=t, **{kw: sgu[c]})
+            cands["down" + n] = lambda c, t=t: ops.moe_grouped_gemm(
+                hs[c], qd[c], routes[c], down=True, out=ys[c], tiles=t, **{kw: sd[c]})
+        cands["gate_up_tile_bf16"] = lambda c: ops.moe_grouped_gemm(
+            x, wgu[c], routes[c], out=hs[c], tiles=True)
+        cands["down_tile_bf16"] = lambda c: ops.moe_grouped_gemm(
+            hs[c], wd[c], routes[c], down=True, out=ys[c], tiles=True)
+        graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
+                  for n, f in cands.items()}
+        samples = {n: [] for n in cands}
+        reps = 10 if T <= 2048 else 3                 # the 32-row kernel takes tens of ms up there
+        for _ in range(7):                            # interleaved: same box, same minute
+            for n in cands:
+                samples[n].append(bm._timed(torch, graphs[n], reps) / copies)
+        P = T * k
+        flop = {"moe": 6 * P * H * I, "gate_up": 4 * P * H * I, "down": 2 * P * H * I}
+        row = {"T": T, "mean_rows_per_expert": round(P / E, 2),
+               "hit_experts_per_layer": round(hit, 2), "copies": copies,
+               "expert_MB_touched": round(touched / 1e6, 1),
+               "weight_bytes_vs_bf16": round(byte_ratio, 4),
+               "max_abs_diff_vs_loop": {n: round(v, 4) for n, v in err.items()},
+               "max_abs_loop": round(ref.abs().max().item(), 3)}
+        for n in cands:
+            us = statistics.median(samples[n])
+            base = n.replace("_tile_bf16", "").replace("_tile", "").replace("loop", "moe")
+            row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
+                      "max_us": round(max(samples[n]), 2),
+                      "TFLOPs": round(flop[base] / us / 1e6, 1)}
+        for n in ("moe", "gate_up", "down"):
+            t, s, b = row[n + "_tile"], row[n], row[n + "_tile_bf16"]
+            t["vs_" + n] = round(t["us"] / s["us"], 3)
+            # the min-max ranges of the rounds do not overlap
+            t["separated"] = bool(t["max_us"] < s["min_us"] or s["max_us"] < t["min_us"])
+            t["vs_bf16_tile"] = round(t["us"] / b["us"], 3)
+            t["separated_from_bf16_tile"] = bool(t["max_us"] < b["min_us"]
+                                                 or b["max_us"] < t["min_us"])
+        row["moe_tile"]["vs_loop"] = round(row["moe_tile"]["us"] / row["loop"]["us"], 3)
+        row["moe"]["vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        print(f"{name:14s} {fmt} T={T:5d} rows/expert {P / E:7.1f}  moe {row['moe']['us']:10.1f} us"
+              f"  moe_tile {row['moe_tile']['us']:10.1f} us ({row['moe_tile']['TFLOPs']:.0f} TF, "
+              f"x{row['moe_tile']['vs_moe']:.3f} of moe, sep {row['moe_tile']['separated']}, "
+              f"x{row['moe_tile']['vs_bf16_tile']:.3f} of the bf16 tiles "
+              f"{row['moe_tile_bf16']['us']:.1f})  loop {row['loop']['us']:10.1f} us  gate_up "
+              f"{row['gate_up']['us']:.1f} -> {row['gate_up_tile']['us']:.1f} "
+              f"(bf16 {row['gate_up_tile_bf16']['us']:.1f})  down {row['down']['us']:.1f} -> "
+              f"{row['down_tile']['us']:.1f} (bf16 {row['down_tile_bf16']['us']:.1f})", flush=True)
+        bm._save(a, f"moe_tile_{fmt}.json", res)
+        del graphs
+        torch.cuda.empty_cache()
+    del qgu, sgu, qd, sd, wgu, wd
+    torch.cuda.empty_cache()
+
+
 def bench_shared(torch, ops, F, name, rows, res, a):
     """The Qwen2-MoE block with its shared expert, fused against unfused (module docstring)."""
     from distributed_llm_inference.config import PRESETS
@@ -403,14 +556,17 @@ def main():
                          "kernel and the loop (moe_tile.json)")
     ap.add_argument("--note", default="", help="free text kept in the result file (--fp8 / --fp4)")
     a = ap.parse_args()
-    if (a.shared or a.tile) and (a.fp8 or a.fp4):
-        ap.error("--shared / --tile measure bf16 weights: not with --fp8 / --fp4")
+    if a.shared and (a.fp8 or a.fp4):
+        ap.error("--shared measures bf16 weights: not with --fp8 / --fp4")
+    if a.tile and a.fp8 and a.fp4:
+        ap.error("--tile measures one quantised format per run: --fp8 or --fp4")
     if a.shared and a.tile:
         ap.error("--shared or --tile, not both")
     a.models = a.models or ("qwen1.5-moe-a2.7b,qwen2-57b-a14b" if a.shared
                             else "qwen3-30b-a3b,mixtral-8x7b")
-    a.rows = a.rows or ("1,4,32,512" if a.shared else "64,512,2048,8192" if a.tile
-                        else "1,8,64,512")
+    tile_q = a.tile and (a.fp8 or a.fp4)
+    a.rows = a.rows or ("1,4,32,512" if a.shared else "128,512,2048,8192" if tile_q
+                        else "64,512,2048,8192" if a.tile else "1,8,64,512")
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
     import torch.nn.functional as F
@@ -422,7 +578,7 @@ def main():
                                   "index_add_ (fp32); routing on the host, not timed",
                           "route / gate_up / down / combine": "moe's launches, each alone"},
            "models": {}}
-    if a.fp8 or a.fp4:
+    if (a.fp8 or a.fp4) and not a.tile:
         res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
                        "`copies` layers); expert_TBps = the hit experts' weight bytes in the "
                        "candidate's format (fp8: plus their fp32 row scales) / time; vs_bf16 = "
@@ -431,7 +587,7 @@ def main():
                                                      "two grouped GEMMs alone)",
                              "moe_fp8 / gate_up_fp8 / down_fp8": "the same on "
                              "ops.quantize_expert_weights_fp8 of the same tensors"}
-    if a.fp4:
+    if a.fp4 and not a.tile:
         res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays over "
                        "`copies` layers); expert_TBps = the hit experts' weight bytes in the "
                        "candidate's format (fp8: plus their fp32 row scales; fp4: 17/32 byte per "
@@ -463,6 +619,21 @@ def main():
             "loop": "per hit expert: index_select, F.linear, swiglu, F.linear, index_add_ "
                     "(fp32); routing on the host, not timed",
             "gate_up / down, gate_up_tile / down_tile": "the two products alone, on either kernel"}
+    if tile_q:
+        fmt = "MXFP4" if a.fp4 else "fp8"
+        res["unit"] += ("; vs_bf16_tile = time / the bf16 tile kernel's on the dequantised "
+                        "weights; weight_bytes_vs_bf16 = the expert bytes behind it / the bf16 ones")
+        res["weight_format"] = fmt
+        res["candidates"] = {
+            "moe": f"moe_route, both grouped products on the weight-streaming kernel (32-row "
+                   f"tiles) on {fmt} experts, moe_combine: what runs with moe_tile_rows_q = 0",
+            "moe_tile": f"the same launches with both products on the {fmt} MFMA tile GEMM "
+                        "(128-row tiles, moe_tile.hip; the weights widened at fragment-read time)",
+            "moe_tile_bf16": "the bf16 tile GEMM on the dequantised weights",
+            "loop": "per hit expert on the dequantised bf16 weights: index_select, F.linear, "
+                    "swiglu, F.linear, index_add_ (fp32); routing on the host, not timed",
+            "gate_up / down, gate_up_tile / down_tile, gate_up_tile_bf16 / down_tile_bf16":
+                "the two products alone, on each kernel"}
     if (a.fp8 or a.fp4 or a.shared or a.tile) and a.note:
         res["note"] = a.note
     with torch.no_grad():
@@ -470,6 +641,11 @@ def main():
             if a.shared:
                 bench_shared(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
                              res, a)
+                continue
+            if tile_q:      # tiles=True on quantised experts needs the knob set
+                with ops.kernel_policy(moe_tile_rows_q=32):
+                    bench_tile_q(torch, ops, F, name.strip(),
+                                 [int(r) for r in a.rows.split(",")], res, a)
                 continue
             if a.tile:
                 bench_tile(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
