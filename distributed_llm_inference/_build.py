@@ -29,7 +29,8 @@ ARCH = os.environ.get("DLI_OFFLOAD_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 KERNEL_SOURCES = ["kernels/norm.hip", "kernels/activation.hip", "kernels/rope_cache.hip",
-                  "kernels/attention.hip", "kernels/attn_prefill32.hip", "kernels/sampling.hip", "kernels/quant.hip",
+                  "kernels/attention.hip", "kernels/attn_prefill32.hip", "kernels/sampling.hip", "kernels/penalty.hip",
+                  "kernels/quant.hip",
                   "kernels/gemv.hip", "kernels/gemm_tile.hip", "kernels/gemm4.hip",
                   "kernels/gemm_fp4.hip", "kernels/gemm_fp4_small.hip", "kernels/gemm_fp8_small.hip",
                   "kernels/moe.hip", "kernels/moe_tile.hip", "kernels/int8_outlier.hip", "kernels/digest.hip"]

@@ -93,7 +93,8 @@ def engine_config(a):
                           window_length=a.window, num_sink_tokens=a.sinks, dtype=a.kv_dtype),
         serve=ServeConfig(max_batch_size=a.max_batch, max_num_batched_tokens=a.max_batched_tokens,
                           num_micro_batches=a.micro_batches, max_seq_len=a.max_seq_len,
-                          use_graphs=not a.no_graphs))
+                          use_graphs=not a.no_graphs,
+                          penalty_slots=_penalty_slots(a)))
 
 
 def load_tokenizer(path: Optional[str]):
@@ -248,7 +249,10 @@ def cmd_worker(a) -> int:
                 raise SystemExit("no prompts (use --prompt-ids 1,2,3 or --prompt TEXT)")
             params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature,
                                     top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed,
-                                    ignore_eos=a.ignore_eos)
+                                    ignore_eos=a.ignore_eos, min_p=a.min_p,
+                                    repetition_penalty=a.repetition_penalty,
+                                    presence_penalty=a.presence_penalty,
+                                    frequency_penalty=a.frequency_penalty)
             outs = replica_generate(drv, prompts, params)
             for s in outs or []:
                 rec = {"prompt_ids": s.prompt, "output_ids": s.output,
@@ -307,6 +311,32 @@ def _gen_args(ap):
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--sample-seed", type=int, default=None)
     ap.add_argument("--ignore-eos", action="store_true")
+    ap.add_argument("--min-p", type=float, default=0.0,
+                    help="drop tokens below this fraction of the most likely token's probability")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="> 0, 1 = off; over prompt and generated tokens (needs --penalty-slots)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0,
+                    help="[-2, 2], 0 = off; over generated tokens (needs --penalty-slots)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0,
+                    help="[-2, 2], 0 = off; per occurrence of a generated token (needs "
+                         "--penalty-slots)")
+
+
+SERVE_PENALTY_SLOTS = 64
+
+
+def _penalty_slots_arg(ap):
+    ap.add_argument("--penalty-slots", type=int, default=None,
+                    help="running sequences that can use repetition / presence / frequency "
+                         "penalties at once (an int32 [slots, vocab] table on the sampling GPU; "
+                         "0 = off, such requests are refused; default 0 for generate, "
+                         f"{SERVE_PENALTY_SLOTS} for serve)")
+
+
+def _penalty_slots(a) -> int:
+    if getattr(a, "penalty_slots", None) is not None:
+        return max(0, a.penalty_slots)
+    return SERVE_PENALTY_SLOTS if getattr(a, "action", getattr(a, "cmd", "")) == "serve" else 0
 
 
 def _serve_args(ap):
@@ -326,9 +356,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     g = sub.add_parser("generate", help="offline generation")
     _common(g)
     _gen_args(g)
+    _penalty_slots_arg(g)
     s = sub.add_parser("serve", help="HTTP server (rank 0) over the pipeline")
     _common(s)
     _serve_args(s)
+    _penalty_slots_arg(s)
     b = sub.add_parser("bench", help="headline benchmark (bench.py) on N GPUs")
     b.add_argument("--gpus", type=int, default=1)
     b.add_argument("--dp", type=int, default=1, help="pipeline replicas (DP x PP)")
@@ -369,6 +401,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     _common(w)
     _gen_args(w)
     _serve_args(w)
+    _penalty_slots_arg(w)
     w.add_argument("--action", required=True)
     a = ap.parse_args(argv)
     if a.cmd == "plan":

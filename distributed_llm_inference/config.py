@@ -781,5 +781,9 @@ class ServeConfig:
     # decode steps' LM head + sampling on every pipeline rank in turn (runtime/head.py) instead of
     # the last stage only; env DLI_HEAD_ROTATION=0/1 overrides
     head_rotation: bool = True
+    # rows of the sampling rank's penalty table (int32 [slots, vocab]) = running sequences that
+    # can use repetition / presence / frequency penalties at once; 0 = no table, no penalty
+    # kernels anywhere, and such requests are refused (min_p needs no slot)
+    penalty_slots: int = 0
     graph_batch_sizes: List[int] = field(default_factory=lambda: [1, 2, 4, 8, 16, 32, 64, 96, 128,
                                                                   160, 192, 224, 256])

@@ -401,7 +401,8 @@ void attn_prefill(Tensor out, Tensor q, optional<Tensor> q_sink, Tensor k_cache,
 // ------------------------------------------------------------------------------ sampling
 void sample(Tensor out_tokens, optional<Tensor> out_logprobs, Tensor logits,
             optional<Tensor> temperature, optional<Tensor> top_k, optional<Tensor> top_p,
-            optional<Tensor> seeds, optional<Tensor> step, optional<Tensor> ctr) {
+            optional<Tensor> seeds, optional<Tensor> step, optional<Tensor> ctr,
+            optional<Tensor> min_p) {
   CHECK_DEV(logits);
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V] row-major");
   TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
@@ -422,6 +423,7 @@ void sample(Tensor out_tokens, optional<Tensor> out_logprobs, Tensor logits,
   };
   p.temperature = opt_f(temperature, "temperature");
   p.top_p = opt_f(top_p, "top_p");
+  p.min_p = opt_f(min_p, "min_p");
   if (top_k.has_value()) {
     CHECK_IN(*top_k); CHECK_I32(*top_k);
     TORCH_CHECK(top_k->numel() == B, "top_k must have B entries");
@@ -449,6 +451,92 @@ void sample(Tensor out_tokens, optional<Tensor> out_logprobs, Tensor logits,
   }
   const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   check_rc(dli::launch_sample(p, (int)B, cur_stream()), "sample");
+}
+
+// ------------------------------------------------------------------------------ penalties
+static void check_penalty_table(const Tensor& table) {
+  CHECK_DEV(table);
+  TORCH_CHECK(table.scalar_type() == at::kInt, "penalty table must be int32");
+  TORCH_CHECK(table.dim() == 2 && table.is_contiguous(),
+              "penalty table must be a contiguous [slots, V] tensor");
+}
+
+void penalty_apply(Tensor logits, Tensor table, Tensor pen_slot, Tensor rep, Tensor pres,
+                   Tensor freq) {
+  CHECK_DEV(logits);
+  check_penalty_table(table);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [B, V] row-major");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
+              "logits must be bf16 or f32");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(table.size(1) == logits.size(1), "penalty table is [slots, ", table.size(1),
+              "] but the logits have V = ", logits.size(1));
+  TORCH_CHECK(B == 0 || logits.stride(0) >= logits.size(1), "logits rows overlap");
+  CHECK_IN(pen_slot); CHECK_I32(pen_slot);
+  CHECK_IN(rep); CHECK_F32(rep); CHECK_IN(pres); CHECK_F32(pres); CHECK_IN(freq); CHECK_F32(freq);
+  TORCH_CHECK(pen_slot.numel() == B && rep.numel() == B && pres.numel() == B && freq.numel() == B,
+              "pen_slot / rep / pres / freq must have B entries");
+  dli::PenaltyParams p{};
+  p.logits = logits.data_ptr();
+  p.logits_is_f32 = logits.scalar_type() == at::kFloat;
+  p.row_stride = logits.stride(0);
+  p.V = (int)logits.size(1);
+  p.table = table.data_ptr<int>();
+  p.slots = (int)table.size(0);
+  p.pen_slot = pen_slot.data_ptr<int>();
+  p.rep = rep.data_ptr<float>();
+  p.pres = pres.data_ptr<float>();
+  p.freq = freq.data_ptr<float>();
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  check_rc(dli::launch_penalty_apply(p, (int)B, cur_stream()), "penalty_apply");
+}
+
+// segments: (slot, kind, reset, n) over the flat ``tokens`` (host list: checked here, then one
+// small upload; this is the eager prefill-time path).  The kernels zero every reset row before
+// they feed any segment, so a reset must be the first segment of its slot in the list
+void penalty_feed(Tensor table, std::vector<std::vector<int64_t>> segments, Tensor tokens) {
+  check_penalty_table(table);
+  CHECK_IN(tokens); CHECK_I32(tokens);
+  TORCH_CHECK(tokens.device() == table.device(), "tokens must be on the table's device");
+  const int64_t slots = table.size(0), n_seg = (int64_t)segments.size();
+  if (n_seg == 0) return;
+  Tensor segs = at::empty({n_seg, 5}, at::TensorOptions().dtype(at::kInt));
+  int* sp = segs.data_ptr<int>();
+  int64_t first = 0, max_n = 0;
+  std::vector<char> fed((size_t)slots, 0);
+  for (int64_t i = 0; i < n_seg; ++i) {
+    const auto& s = segments[i];
+    TORCH_CHECK(s.size() == 4, "penalty_feed: a segment is (slot, kind, reset, n)");
+    TORCH_CHECK(s[0] >= 0 && s[0] < slots, "penalty_feed: slot ", s[0], " outside the table's ",
+                slots, " slots");
+    TORCH_CHECK(s[1] == 0 || s[1] == 1, "penalty_feed: kind must be 0 (prompt) or 1 (output)");
+    TORCH_CHECK(s[3] >= 0, "penalty_feed: negative segment length");
+    TORCH_CHECK(!(s[2] && fed[(size_t)s[0]]), "penalty_feed: the reset of slot ", s[0],
+                " must be the first segment of that slot");
+    fed[(size_t)s[0]] = 1;
+    sp[i * 5 + 0] = (int)s[0]; sp[i * 5 + 1] = (int)s[1]; sp[i * 5 + 2] = s[2] ? 1 : 0;
+    sp[i * 5 + 3] = (int)first; sp[i * 5 + 4] = (int)s[3];
+    first += s[3];
+    max_n = std::max(max_n, s[3]);
+  }
+  TORCH_CHECK(first == tokens.numel(), "penalty_feed: the segments cover ", first,
+              " tokens but ", tokens.numel(), " were given");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(table.device());
+  Tensor dsegs = segs.to(table.device());
+  check_rc(dli::launch_penalty_feed(table.data_ptr<int>(), (int)slots, (int)table.size(1),
+                                    dsegs.data_ptr<int>(), (int)n_seg, tokens.data_ptr<int>(),
+                                    (int)max_n, cur_stream()), "penalty_feed");
+}
+
+void penalty_update(Tensor table, Tensor pen_slot, Tensor tokens) {
+  check_penalty_table(table);
+  CHECK_IN(pen_slot); CHECK_I32(pen_slot); CHECK_IN(tokens); CHECK_I32(tokens);
+  TORCH_CHECK(pen_slot.numel() == tokens.numel(), "pen_slot and tokens must have B entries");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(table.device());
+  check_rc(dli::launch_penalty_update(table.data_ptr<int>(), (int)table.size(0),
+                                      (int)table.size(1), pen_slot.data_ptr<int>(),
+                                      tokens.data_ptr<int>(), (int)tokens.numel(), cur_stream()),
+           "penalty_update");
 }
 
 // ------------------------------------------------------------------------------ fp8 quant
@@ -1489,7 +1577,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qb"), py::arg("mask") = py::none(), py::arg("m32") = true);
   m.def("sample", &sample, "greedy / temperature / top-k / top-p sampling", py::arg("out_tokens"),
         py::arg("out_logprobs"), py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
-        py::arg("top_p"), py::arg("seeds"), py::arg("step"), py::arg("ctr") = py::none());
+        py::arg("top_p"), py::arg("seeds"), py::arg("step"), py::arg("ctr") = py::none(),
+        py::arg("min_p") = py::none());
+  m.def("penalty_apply", &penalty_apply, "repetition / presence / frequency penalties, in place",
+        py::arg("logits"), py::arg("table"), py::arg("pen_slot"), py::arg("rep"), py::arg("pres"),
+        py::arg("freq"));
+  m.def("penalty_feed", &penalty_feed, "reset slots and feed prompt / output tokens to the table",
+        py::arg("table"), py::arg("segments"), py::arg("tokens"));
+  m.def("penalty_update", &penalty_update, "count the sampled tokens of the rows with a slot",
+        py::arg("table"), py::arg("pen_slot"), py::arg("tokens"));
   m.def("digest", &digest, "hop-integrity payload digest partials", py::arg("part"), py::arg("t"));
   m.def("quant_rowwise", &quant_rowwise, "row-wise fp8 e4m3 quantisation (+fused RMSNorm)",
         py::arg("q_out"), py::arg("scale"), py::arg("x"), py::arg("residual"), py::arg("norm_w"),

@@ -80,7 +80,33 @@ struct SampleParams {
                             // sequence) or nullptr: then (step, row) key the randomness
   int* out_tokens;          // [B]
   float* out_logprobs;      // [B] or nullptr
+  const float* min_p;       // [B] or nullptr: keep x >= max(x) + ln(min_p) (<= 0: disabled;
+                            // ignored by greedy rows); nullptr selects the kernels without it
 };
+
+// Penalty table (penalty.hip): int32 [slots, V] per sampling rank, one slot per running sequence;
+// bit 31 of a word = "token is in the prompt", bits 0-30 = times the token was generated
+struct PenaltyParams {
+  void* logits;             // [B, row_stride] bf16 or f32, edited in place
+  int logits_is_f32;
+  long row_stride;
+  int V;
+  const int* table;         // [slots, V]
+  int slots;
+  const int* pen_slot;      // [B] (-1, or any value outside [0, slots): row untouched)
+  const float* rep;         // [B] repetition penalty (1 = off)
+  const float* pres;        // [B] presence penalty (0 = off)
+  const float* freq;        // [B] frequency penalty (0 = off)
+};
+int launch_penalty_apply(const PenaltyParams& p, int B, hipStream_t stream);
+// segs [n_seg][5] = (slot, kind, reset, first token, n): zero the rows of the segments with
+// reset (all of them first: the binding rejects a reset after another segment of its slot),
+// then kind 0 sets bit 31 of each token's word, kind 1 adds one per occurrence
+int launch_penalty_feed(int* table, int slots, int V, const int* segs, int n_seg,
+                        const int* tokens, int max_n, hipStream_t stream);
+// table[pen_slot[b]][tokens[b]] += 1 for the rows with a slot
+int launch_penalty_update(int* table, int slots, int V, const int* pen_slot, const int* tokens,
+                          int B, hipStream_t stream);
 
 int launch_rms_norm(bf16* out, const bf16* x, const bf16* residual_in, bf16* residual_out,
                     const bf16* w, float eps, int rows, int hidden, hipStream_t stream,

@@ -48,6 +48,15 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned lon
   return ((float)(r >> 41) + 0.5f) * (1.0f / 8388608.0f);
 }
 
+// min-p threshold on x: keep x >= mx + ln(m), i.e. prob >= m * max prob (m <= 0: -inf, keeps
+// all).  The loops compare the rounded product x = v * inv_t itself against this - the row
+// maximum mx is the same product of the largest element, so at m = 1 exactly the maximum value
+// group is kept; "x - mx >= ln m" would contract into an fma whose result for the maximum is the
+// product's rounding error, not 0
+__device__ __forceinline__ float min_p_threshold(float m, float mx) {
+  return m > 0.f ? mx + logf(m) : -INFINITY;
+}
+
 // block argmax of (value, index) pairs; lower index wins ties.
 __device__ __forceinline__ void argmax_pair(float& v, int& idx, float ov, int oi) {
   if (ov > v || (ov == v && oi < idx)) {
@@ -109,7 +118,7 @@ __device__ __forceinline__ void block_reduce_sum3(float& a, float& b, float& c, 
 // histograms built with LDS atomics (which serialise: most of a row shares a few exponent bins).
 // Same kept set as the radix select (the largest threshold whose count reaches k / whose mass
 // reaches top_p x the kept mass, ties at it kept), same Gumbel-max draw, deterministic sums.
-template <int NV>
+template <int NV, bool MINP>
 __device__ __forceinline__ void sample_row_regs(const SampleParams& p, int row, float temp) {
   __shared__ float sc[48];
   __shared__ float s_f[16];
@@ -232,6 +241,8 @@ __device__ __forceinline__ void sample_row_regs(const SampleParams& p, int row, 
             : (st * 0x100000001B3ull) ^ ((unsigned long long)row << 40);
   float best = -INFINITY;
   int bi = 0x7fffffff;
+  float x_min = -INFINITY;   // min-p: keep x >= x_min
+  if constexpr (MINP) x_min = min_p_threshold(p.min_p[row], mx);
   pin();
 #pragma unroll
   for (int u = 0; u < NV; ++u) {
@@ -240,6 +251,8 @@ __device__ __forceinline__ void sample_row_regs(const SampleParams& p, int row, 
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       if (key(u, e) < thr) continue;
+      if constexpr (MINP)
+        if (!(fval(u, e) * inv_t >= x_min)) continue;
       const float uu = uniform01(seed, base + (unsigned long long)(i0 + e));
       argmax_pair(best, bi, fval(u, e) * inv_t - __logf(-__logf(uu)), i0 + e);
     }
@@ -261,8 +274,10 @@ __device__ __forceinline__ void sample_row_regs(const SampleParams& p, int row, 
 }
 
 // NV > 0: bf16 rows of at most NV * 8 * 1024 values (V % 8 == 0) take the register path for
-// temperature > 0 (sample_row_regs); NV == 0: the radix-histogram path below
-template <int NV>
+// temperature > 0 (sample_row_regs); NV == 0: the radix-histogram path below.  MINP: the
+// Gumbel-max loops also apply the min-p predicate (SampleParams::min_p != nullptr); without it
+// the instantiations are the ones the sampler had before min-p existed
+template <int NV, bool MINP>
 __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
   const int row = blockIdx.x;
   const int V = p.V;
@@ -316,7 +331,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
     return;
   }
   if constexpr (NV > 0) {
-    sample_row_regs<NV>(p, row, temp);
+    sample_row_regs<NV, MINP>(p, row, temp);
     return;
   }
   const float inv_t = 1.f / temp;
@@ -408,9 +423,13 @@ __global__ void __launch_bounds__(1024) sample_kernel(SampleParams p) {
             : (st * 0x100000001B3ull) ^ ((unsigned long long)row << 40);
   float best = -INFINITY;
   int bi = 0x7fffffff;
+  float x_min = -INFINITY;   // min-p: keep x >= x_min
+  if constexpr (MINP) x_min = min_p_threshold(p.min_p[row], mx);
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
     const float x = load_logit(p, row, i) * inv_t;
     if (f2key(x) < thr_key) continue;
+    if constexpr (MINP)
+      if (!(x >= x_min)) continue;
     const float u = uniform01(seed, base + (unsigned long long)i);
     const float g = -__logf(-__logf(u));
     argmax_pair(best, bi, x + g, i);
@@ -432,14 +451,25 @@ int launch_sample(const SampleParams& p, int B, hipStream_t stream) {
   // 16-byte row loads: a [B, V] view may start anywhere in its buffer
   const bool regs = !p.logits_is_f32 && p.V % 8 == 0 && p.row_stride % 8 == 0 &&
                     reinterpret_cast<uintptr_t>(p.logits) % 16 == 0;
+  if (p.min_p) {
+    if (regs && n8 <= 4 * 1024)
+      sample_kernel<4, true><<<B, 1024, 0, stream>>>(p);
+    else if (regs && n8 <= 8 * 1024)
+      sample_kernel<8, true><<<B, 1024, 0, stream>>>(p);
+    else if (regs && n8 <= 16 * 1024)
+      sample_kernel<16, true><<<B, 1024, 0, stream>>>(p);
+    else
+      sample_kernel<0, true><<<B, 1024, 0, stream>>>(p);
+    return 0;
+  }
   if (regs && n8 <= 4 * 1024)
-    sample_kernel<4><<<B, 1024, 0, stream>>>(p);
+    sample_kernel<4, false><<<B, 1024, 0, stream>>>(p);
   else if (regs && n8 <= 8 * 1024)
-    sample_kernel<8><<<B, 1024, 0, stream>>>(p);
+    sample_kernel<8, false><<<B, 1024, 0, stream>>>(p);
   else if (regs && n8 <= 16 * 1024)
-    sample_kernel<16><<<B, 1024, 0, stream>>>(p);
+    sample_kernel<16, false><<<B, 1024, 0, stream>>>(p);
   else
-    sample_kernel<0><<<B, 1024, 0, stream>>>(p);
+    sample_kernel<0, false><<<B, 1024, 0, stream>>>(p);
   return 0;
 }
 

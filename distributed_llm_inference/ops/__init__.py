@@ -406,19 +406,69 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
            seeds: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, logprobs: Optional[torch.Tensor] = None,
            generator: Optional[torch.Generator] = None,
-           counters: Optional[torch.Tensor] = None) -> torch.Tensor:
+           counters: Optional[torch.Tensor] = None,
+           min_p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``seeds`` + ``counters`` (int64 per row: the sampled token's position in its sequence) key
     each row's randomness, so a seeded request samples the same tokens in any batch / pipeline;
     without ``counters`` the device ``step`` and the row index do.  ``logits`` may be any
-    [B, V] view with unit column stride; ``top_p <= 0`` keeps the maximum value group."""
+    [B, V] view with unit column stride; ``top_p <= 0`` keeps the maximum value group.
+    ``min_p`` (f32 per row, 0 = off): also drop tokens whose probability is below ``min_p`` times
+    the most likely token's, i.e. keep ``x >= max(x) + ln(min_p)`` with ``x = logits / T``; the
+    kept set is top-k ∩ top-p ∩ min-p.  Greedy rows ignore it; ``None`` runs the kernels
+    without the predicate."""
     if not _gpu(logits):
         y = ref.sample(logits, temperature, top_k, top_p, generator, seeds=seeds, step=step,
-                       counters=counters)
+                       counters=counters, min_p=min_p)
         return out.copy_(y) if out is not None else y
     if out is None:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    native().sample(out, logprobs, logits, temperature, top_k, top_p, seeds, step, counters)
+    native().sample(out, logprobs, logits, temperature, top_k, top_p, seeds, step, counters, min_p)
     return out
+
+
+# ----------------------------------------------------------------------------- penalties
+# Penalty table: int32 [slots, V] on the sampling rank, one slot per running sequence; bit 31 of
+# a word = "token is in the prompt", bits 0-30 = times the token was generated (penalty.hip)
+PENALTY_PROMPT_BIT = ref.PENALTY_PROMPT_BIT
+
+
+def penalty_table(slots: int, vocab_size: int, device) -> torch.Tensor:
+    return torch.zeros(slots, vocab_size, dtype=torch.int32, device=device)
+
+
+def apply_penalties(logits: torch.Tensor, table: torch.Tensor, pen_slot: torch.Tensor,
+                    rep: torch.Tensor, pres: torch.Tensor, freq: torch.Tensor) -> torch.Tensor:
+    """Penalise ``logits`` [B, V] (bf16 or f32) in place, before the temperature, for the rows
+    with ``pen_slot[b] >= 0``: a token of the slot's prompt or outputs gets ``l > 0 ? l / rep :
+    l * rep``; one generated n > 0 times gets ``l - freq * n - pres``.  fp32 arithmetic, one
+    rounding at the store; elements of unseen tokens (and rows without a slot) are not written."""
+    if not _gpu(logits):
+        return ref.apply_penalties(logits, table, pen_slot, rep, pres, freq)
+    native().penalty_apply(logits, table, pen_slot, rep, pres, freq)
+    return logits
+
+
+def penalty_feed(table: torch.Tensor, segments, tokens) -> None:
+    """Feed tokens that enter the cache as prefill chunks: ``segments`` is a list of
+    ``(slot, kind, reset, n)`` over the flat ``tokens`` (list or int32 tensor).  ``reset`` zeroes
+    the slot's row first (it must be the first segment of its slot in the list); ``kind`` 0 marks prompt tokens, 1 counts earlier outputs (duplicates
+    count).  Runs eagerly on the current stream."""
+    segments = [[int(v) for v in s] for s in segments]
+    if not segments:
+        return
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.tensor(list(tokens), dtype=torch.int32)
+    if not _gpu(table):
+        return ref.penalty_feed(table, segments, tokens)
+    native().penalty_feed(table, segments, tokens.to(table.device))
+
+
+def penalty_update(table: torch.Tensor, pen_slot: torch.Tensor, tokens: torch.Tensor) -> None:
+    """``table[pen_slot[b], tokens[b]] += 1`` for the rows with a slot (after the sampler, in the
+    same launch sequence)."""
+    if not _gpu(table):
+        return ref.penalty_update(table, pen_slot, tokens)
+    native().penalty_update(table, pen_slot, tokens)
 
 
 # ----------------------------------------------------------------------------- fp8

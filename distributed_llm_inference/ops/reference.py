@@ -240,7 +240,8 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
            top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
            generator: Optional[torch.Generator] = None, seeds: Optional[torch.Tensor] = None,
            step: Optional[torch.Tensor] = None,
-           counters: Optional[torch.Tensor] = None) -> torch.Tensor:
+           counters: Optional[torch.Tensor] = None,
+           min_p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """With ``seeds`` (one per row) each row draws from its own generator seeded by
     (seed, counter) — ``counters[b]`` (the token's position in its sequence) or else ``step`` —
     like the HIP kernel's counter-based hash: a sequence's samples do not depend on which other
@@ -261,6 +262,9 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
             out[b] = int(torch.argmax(x))
             continue
         x = x / t
+        m = float(min_p[b]) if min_p is not None else 0.0
+        # min-p on the unfiltered row: prob >= m * max prob  <=>  x >= max(x) + ln(m)
+        drop = (x - x.max() < math.log(m)) if m > 0 else None
         k = int(top_k[b]) if top_k is not None else 0
         if 0 < k < V:
             thr = torch.topk(x, k).values[-1]
@@ -273,9 +277,70 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
             keep_n = int(torch.searchsorted(cum, torch.tensor(p * float(cum[-1])))) + 1
             thr = sp[min(keep_n, V) - 1]
             x = x.masked_fill(probs < thr, float("-inf"))
+        if drop is not None:
+            x = x.masked_fill(drop, float("-inf"))
         probs = torch.softmax(x, -1)
         out[b] = int(torch.multinomial(probs, 1, generator=g))
     return out
+
+
+# ----------------------------------------------------------------------------- penalties
+PENALTY_PROMPT_BIT = -(1 << 31)     # bit 31 of an int32 table word: the token is in the prompt
+_COUNT_MASK = 0x7FFFFFFF
+
+
+def apply_penalties(logits: torch.Tensor, table: torch.Tensor, pen_slot: torch.Tensor,
+                    rep: torch.Tensor, pres: torch.Tensor, freq: torch.Tensor) -> torch.Tensor:
+    """torch counterpart of penalty.hip's ``penalty_apply`` (in place): fp32 steps, the
+    frequency term as one multiply-add (evaluated in fp64 and rounded once), one rounding to the
+    logits' dtype, and only the elements of seen tokens are written."""
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != logits.shape[1]:
+        raise ValueError("penalty table must be int32 [slots, V] with the logits' V")
+    for b in range(logits.shape[0]):
+        slot = int(pen_slot[b])
+        if slot < 0 or slot >= table.shape[0]:
+            continue
+        w = table[slot]
+        seen = w != 0
+        if not bool(seen.any()):
+            continue
+        n = (w[seen] & _COUNT_MASK).to(torch.float32)
+        r, f, p = (torch.tensor(float(t[b]), dtype=torch.float32) for t in (rep, freq, pres))
+        l = logits[b][seen].to(torch.float32)
+        l = torch.where(l > 0, l / r, l * r)
+        l = (l.double() - f.double() * n.double()).to(torch.float32)
+        l = torch.where(n > 0, l - p, l)
+        logits[b][seen] = l.to(logits.dtype)
+    return logits
+
+
+def penalty_feed(table: torch.Tensor, segments, tokens: torch.Tensor) -> None:
+    toks = tokens.reshape(-1).tolist()
+    if sum(int(s[3]) for s in segments) != len(toks):
+        raise ValueError("penalty_feed: the segments do not cover the tokens")
+    at = 0
+    fed = set()
+    for slot, kind, reset, n in segments:
+        if not 0 <= slot < table.shape[0]:
+            raise ValueError(f"penalty_feed: slot {slot} outside the table's {table.shape[0]} slots")
+        if reset and slot in fed:   # (the HIP path zeroes every reset row before it feeds any)
+            raise ValueError(f"penalty_feed: the reset of slot {slot} must be the first segment "
+                             "of that slot")
+        fed.add(slot)
+        if reset:
+            table[slot].zero_()
+        for t in toks[at: at + n]:
+            if kind == 0:
+                table[slot, t] |= PENALTY_PROMPT_BIT
+            else:
+                table[slot, t] += 1
+        at += n
+
+
+def penalty_update(table: torch.Tensor, pen_slot: torch.Tensor, tokens: torch.Tensor) -> None:
+    for slot, t in zip(pen_slot.tolist(), tokens.tolist()):
+        if 0 <= slot < table.shape[0]:
+            table[slot, t] += 1
 
 
 # ----------------------------------------------------------------------------- rope table

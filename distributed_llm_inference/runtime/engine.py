@@ -89,6 +89,10 @@ def build_executor(spec: ModelSpec, start: int, end: int, device: torch.device, 
         tdir = os.environ.get("DLI_TUNING_DIR", os.path.join(os.path.dirname(os.path.dirname(
             os.path.dirname(os.path.abspath(__file__)))), "build", "tuning"))
         tune_decode_gemms(stage, buckets, os.path.join(tdir, "tunableop_results.csv"))
+    pen_table = None
+    if sc.penalty_slots > 0 and stage.has_head:
+        # before the KV pool is sized, so that mem_get_info sees it
+        pen_table = ops.penalty_table(sc.penalty_slots, spec.vocab_size, device)
     if num_blocks is None:
         num_blocks = cc.num_blocks
     if num_blocks is None:
@@ -134,7 +138,7 @@ def build_executor(spec: ModelSpec, start: int, end: int, device: torch.device, 
     return StageExecutor(stage, pool, max_num_seqs=sc.max_batch_size,
                          max_num_batched_tokens=sc.max_num_batched_tokens,
                          max_seq_len=sc.max_seq_len, use_graphs=sc.use_graphs,
-                         graph_batch_sizes=sc.graph_batch_sizes)
+                         graph_batch_sizes=sc.graph_batch_sizes, pen_table=pen_table)
 
 
 def make_scheduler(spec: ModelSpec, ex: StageExecutor, cfg: EngineConfig, num_stages: int) -> Scheduler:
@@ -142,7 +146,8 @@ def make_scheduler(spec: ModelSpec, ex: StageExecutor, cfg: EngineConfig, num_st
     M = sc.num_micro_batches or (num_stages + 1 if num_stages > 1 else 1)
     m = ex.pool.manager
     return Scheduler(M, sc.max_batch_size, sc.max_num_batched_tokens, m.blocks_for, m.num_blocks,
-                     eos_token_id=spec.eos_token_id, max_seq_len=sc.max_seq_len)
+                     eos_token_id=spec.eos_token_id, max_seq_len=sc.max_seq_len,
+                     penalty_slots=sc.penalty_slots)
 
 
 class LLMEngine:
@@ -361,7 +366,8 @@ def init_pipeline_rank(cfg: EngineConfig, backend: str = "gloo"):
         # next to in-flight receive kernels or the token publisher thread
         variants = (True, False) if (rotate and srank == pp - 1) else (True,)
         _progress(f"transport up ({type(transport).__name__}); capturing decode graphs")
-        ex.warmup_graphs(variants=variants)
+        # (the min-p variants of the sampling graphs too: a step with a min-p row replays one)
+        ex.warmup_graphs(variants=variants, min_p=True)
         if heads_runner is not None:
             heads_runner.warmup()
         dist.barrier(group=group)

@@ -61,11 +61,33 @@ class StepPlan:
     sample_pos: List[int] = field(default_factory=list)     # sampled token's position (RNG key)
     kind: str = "run"                                       # run | barrier | stop
     tokens: Optional[List[int]] = None                      # stage-0 input (not broadcast)
+    # sampling controls, one per sample row (an empty list = off for every row)
+    min_p: List[float] = field(default_factory=list)
+    pen_slot: List[int] = field(default_factory=list)       # penalty-table row (-1 = none)
+    rep: List[float] = field(default_factory=list)          # repetition penalty (1 = off)
+    pres: List[float] = field(default_factory=list)         # presence penalty (0 = off)
+    freq: List[float] = field(default_factory=list)         # frequency penalty (0 = off)
+    # tokens entering the cache this step as prefill chunks of sequences that own a slot (the
+    # sampling rank sees no prompt otherwise): [slot, kind (0 prompt | 1 output), reset, n]
+    # segments over the flat pen_feed_tokens
+    pen_feed: List[List[int]] = field(default_factory=list)
+    pen_feed_tokens: List[int] = field(default_factory=list)
 
     def __post_init__(self):
         # computed once: both are read several times per step on every stage
         self._num_tokens = int(sum(self.q_lens))
         self._decode = bool(self.seq_ids) and self._num_tokens == len(self.q_lens)
+        self._penalised = any(s >= 0 for s in self.pen_slot)
+        self._min_p = any(m > 0 for m in self.min_p)
+
+    @property
+    def penalised(self) -> bool:
+        """Some sample row owns a penalty slot (such a step samples where the table lives)."""
+        return self._penalised
+
+    @property
+    def uses_min_p(self) -> bool:
+        return self._min_p
 
     @property
     def is_decode(self) -> bool:
@@ -79,7 +101,9 @@ class StepPlan:
         d = dict(step=self.step, mb=self.mb, seq_ids=self.seq_ids, q_lens=self.q_lens,
                  free_ids=self.free_ids, sample_rows=self.sample_rows,
                  temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
-                 seeds=self.seeds, sample_pos=self.sample_pos, kind=self.kind)
+                 seeds=self.seeds, sample_pos=self.sample_pos, kind=self.kind,
+                 min_p=self.min_p, pen_slot=self.pen_slot, rep=self.rep, pres=self.pres,
+                 freq=self.freq, pen_feed=self.pen_feed, pen_feed_tokens=self.pen_feed_tokens)
         return d
 
     @classmethod
@@ -94,6 +118,33 @@ def _fill_pos(dst: torch.Tensor, plan: StepPlan, n: int) -> None:
         dst[:n] = torch.as_tensor(plan.sample_pos, dtype=torch.int64)
     else:
         dst[:n] = plan.step
+
+
+def _fill_rows(dst: torch.Tensor, values, n: int, rows: int, default) -> None:
+    """Per-sample-row control ``values`` into ``dst[:n]`` (``default`` when the plan carries
+    none), and ``default`` in the padded rows ``[n, rows)``."""
+    if len(values) == n and n:
+        dst[:n] = torch.as_tensor(values, dtype=dst.dtype)
+        if rows > n:
+            dst[n:rows] = default
+    else:
+        dst[:rows] = default
+
+
+def stage_min_p(st: "_Staging", plan: StepPlan, n: int, rows: int) -> None:
+    _fill_rows(st.h["min_p"], plan.min_p, n, rows, 0.0)
+    st.upload("min_p", rows)
+
+
+def stage_penalties(st: "_Staging", plan: StepPlan, n: int, rows: int) -> None:
+    """Padded rows get slot -1, repetition 1, presence and frequency 0."""
+    h = st.h
+    _fill_rows(h["pen_slot"], plan.pen_slot, n, rows, -1)
+    _fill_rows(h["rep"], plan.rep, n, rows, 1.0)
+    _fill_rows(h["pres"], plan.pres, n, rows, 0.0)
+    _fill_rows(h["freq"], plan.freq, n, rows, 0.0)
+    for k in ("pen_slot", "rep", "pres", "freq"):
+        st.upload(k, rows)
 
 
 class _Staging:
@@ -114,7 +165,12 @@ class _Staging:
                  ("q_start", torch.int32, (max_seqs + 1,)),
                  ("top_k", torch.int32, (max_seqs,)),
                  ("temperature", torch.float32, (max_seqs,)),
-                 ("top_p", torch.float32, (max_seqs,))]
+                 ("top_p", torch.float32, (max_seqs,)),
+                 ("min_p", torch.float32, (max_seqs,)),
+                 ("pen_slot", torch.int32, (max_seqs,)),
+                 ("rep", torch.float32, (max_seqs,)),
+                 ("pres", torch.float32, (max_seqs,)),
+                 ("freq", torch.float32, (max_seqs,))]
         self.offsets: Dict[str, Tuple[int, torch.dtype, tuple]] = {}
         off = 0
         for name, dt, shape in specs:
@@ -206,7 +262,8 @@ class _Staging:
 class StageExecutor:
     def __init__(self, stage: CausalLMStage, pool: KVPool, max_num_seqs: int = 256,
                  max_num_batched_tokens: int = 8192, max_seq_len: int = 8192,
-                 use_graphs: bool = True, graph_batch_sizes: Optional[Sequence[int]] = None):
+                 use_graphs: bool = True, graph_batch_sizes: Optional[Sequence[int]] = None,
+                 pen_table: Optional[torch.Tensor] = None):
         self.stage = stage
         self.pool = pool
         self.spec = stage.spec
@@ -228,6 +285,14 @@ class StageExecutor:
             if not stage.has_embed else None
         self._sample_out = torch.empty(max_num_seqs, dtype=torch.int32, device=self.device)
         self._wp = pool.attn_params()
+        # penalty table int32 [slots, V] (head-owning stage, ServeConfig.penalty_slots > 0) or
+        # None: then no penalty kernel is ever launched by this executor
+        if pen_table is not None and not stage.has_head:
+            raise ValueError("a penalty table belongs to the stage that samples")
+        self.pen_table = pen_table
+        # what warm-up runs before a capture read instead of the staged slots (see _capture)
+        self._pen_none = torch.full((max_num_seqs,), -1, dtype=torch.int32, device=self.device) \
+            if pen_table is not None else None
         self._step_counter = 0
         # warm-up / capture stream (a pipeline rank passes its dedicated one: runtime/streams.py)
         self.capture_stream: Optional[torch.cuda.Stream] = None
@@ -331,6 +396,10 @@ class StageExecutor:
                 _fill_pos(h["sample_pos"], plan, ns)
                 st.upload("logits_rows", ns)
                 n = ns
+            if plan.uses_min_p:
+                stage_min_p(st, plan, ns, n)
+            if self.pen_table is not None:
+                stage_penalties(st, plan, ns, n)
             st.upload("temperature", n)
             st.upload("top_k", n)
             st.upload("top_p", n)
@@ -376,15 +445,26 @@ class StageExecutor:
 
     # ------------------------------------------------------------------ forward
     def _forward(self, meta: AttnMetadata, inputs: torch.Tensor, n_sample: int,
-                 project: bool = True) -> torch.Tensor:
+                 project: bool = True, min_p: bool = False, warm: bool = False) -> torch.Tensor:
+        """``min_p``: run the sampler with the staged min-p values (else the kernels without the
+        predicate).  ``warm``: a warm-up run before a capture - the penalty kernels read a
+        constant all -1 slot array, so they launch but touch neither the logits nor the table."""
         out = self.stage(inputs, meta, self.pool, project=project)
         if not self.stage.has_head or not project:
             return out
         d = self.staging.d
         tokens = self._sample_out[:n_sample]
+        table = self.pen_table
+        if table is not None:
+            slots = (self._pen_none if warm else d["pen_slot"])[:n_sample]
+            ops.apply_penalties(out, table, slots, d["rep"][:n_sample], d["pres"][:n_sample],
+                                d["freq"][:n_sample])
         ops.sample(out, temperature=d["temperature"][:n_sample], top_k=d["top_k"][:n_sample],
                    top_p=d["top_p"][:n_sample], seeds=d["seeds"][:n_sample], step=d["step"],
-                   out=tokens, counters=d["sample_pos"][:n_sample])
+                   out=tokens, counters=d["sample_pos"][:n_sample],
+                   min_p=d["min_p"][:n_sample] if min_p else None)
+        if table is not None:
+            ops.penalty_update(table, slots, tokens)
         return tokens
 
     def input_buffer(self, plan: StepPlan) -> Optional[torch.Tensor]:
@@ -442,9 +522,13 @@ class StageExecutor:
         self.reserve(plan.seq_ids, plan.q_lens)
         B = len(plan.seq_ids)
         decode = plan.is_decode
+        use_min_p = plan.uses_min_p and self.stage.has_head and project
         grows = self._graph_rows(B) if decode else None
         rows = grows if grows is not None else B
         self._stage_metadata(plan, rows)
+        if self.pen_table is not None and plan.pen_feed:
+            # prompt / recomputed tokens of the sequences that own a slot, before this step samples
+            ops.penalty_feed(self.pen_table, plan.pen_feed, plan.pen_feed_tokens)
         if TRACKER._words is not None:
             TRACKER.note_plan(plan.step, B=B, T=plan.num_tokens, rows=rows,
                               max_len=int(self.staging.h["seq_lens"][:B].max()))
@@ -459,15 +543,18 @@ class StageExecutor:
         project = project or not self.stage.has_head
         if not project and not all_sample:
             raise ValueError("project=False needs a decode step in which every row samples")
+        if plan.penalised and self.stage.has_head and project and self.pen_table is None:
+            raise RuntimeError("a step with penalised rows reached a stage without a penalty "
+                               "table (ServeConfig.penalty_slots)")
         if grows is not None and (not self.stage.has_head or all_sample):
             if not self.stage.has_embed:
                 src = inputs[:B]
                 if src.data_ptr() != self._hidden_in.data_ptr():
                     self._hidden_in[:B].copy_(src)
-            key = grows if project else (grows, "norm")
+            key = self._graph_key(grows, project, use_min_p)
             g = self._graphs.get(key)
             if g is None:
-                g = self._capture(grows, project)
+                g = self._capture(grows, project, use_min_p)
             TRACKER.device_mark("compute_in", plan.step, torch.cuda.current_stream())
             t1 = time.perf_counter()
             HOST.add("stage", (t1 - t0) * 1e3 - (self.staging.waited_ms - w0))
@@ -486,14 +573,27 @@ class StageExecutor:
             x = inputs
         t1 = time.perf_counter()
         HOST.add("stage", (t1 - t0) * 1e3 - (self.staging.waited_ms - w0))
-        out = self._forward(meta, x, n_sample if self.stage.has_head else 0, project)
+        out = self._forward(meta, x, n_sample if self.stage.has_head else 0, project, use_min_p)
         HOST.since("launch", t1)
         return out if project else out[:B]
 
     # ------------------------------------------------------------------ graphs
-    def _capture(self, rows: int, project: bool = True) -> "_GraphEntry":
+    @staticmethod
+    def _graph_key(rows: int, project: bool = True, min_p: bool = False):
+        if not project:
+            return (rows, "norm")
+        return (rows, "min_p") if min_p else rows
+
+    def _capture(self, rows: int, project: bool = True, min_p: bool = False) -> "_GraphEntry":
         """Capture the decode step for ``rows`` sequences (buffers already staged by the caller);
-        ``project=False``: the last stage's variant that ends at the final norm."""
+        ``project=False``: the last stage's variant that ends at the final norm; ``min_p``: the
+        variant whose sampler applies min-p (captured by ``warmup_graphs(min_p=True)``, as a
+        pipeline rank does before any traffic, or else when a step first asks for it).
+
+        A graph captured lazily inside ``_execute`` warms up on the live step's staging, and the
+        penalty count update is not idempotent (a second run would also penalise the token the
+        first one chose): the warm-up runs read a constant all -1 slot array, only the captured
+        launch reads the staged one."""
         splits = self._splits(rows)
         plan_like = StepPlan(0, 0, list(range(rows)), [1] * rows,
                              sample_rows=list(range(rows)))
@@ -506,7 +606,7 @@ class StageExecutor:
         s.wait_stream(cur)
         with torch.cuda.stream(s):
             for _ in range(2):
-                self._forward(meta, x, n_sample, project)
+                self._forward(meta, x, n_sample, project, min_p, warm=True)
         cur.wait_stream(s)
         prime_graph_rng(self.device)
         graph = torch.cuda.CUDAGraph()
@@ -515,25 +615,30 @@ class StageExecutor:
         # thread_local: another thread (token publisher) may synchronise events meanwhile
         with capture_guard(), torch.cuda.graph(graph, pool=self._graph_pool, stream=s,
                                                capture_error_mode="thread_local"):
-            out = self._forward(meta, x, n_sample, project)
+            out = self._forward(meta, x, n_sample, project, min_p)
         cur.wait_stream(s)
         entry = _GraphEntry(graph, out)
-        self._graphs[rows if project else (rows, "norm")] = entry
+        self._graphs[self._graph_key(rows, project, min_p)] = entry
         log.info("captured decode graph rows=%d splits=%d stage=[%d,%d)%s", rows, splits,
                  self.stage.start, self.stage.end, "" if project else " (ends at the final norm)")
         # (the captured run did not execute; the caller replays the graph for the real step)
         return entry
 
     def warmup_graphs(self, sizes: Optional[Sequence[int]] = None,
-                      variants: Sequence[bool] = (True,)) -> None:
+                      variants: Sequence[bool] = (True,), min_p: bool = False) -> None:
         """Pre-capture decode graphs with dummy (empty, seq_len 0) batches.  ``variants``: the
         ``project`` flags to capture (False = the last stage's graph that ends at the final norm,
-        used when the LM head rotates)."""
+        used when the LM head rotates).  ``min_p``: on a stage that samples, also capture each
+        bucket's variant whose sampler applies min-p, so that a step with a min-p row replays a
+        graph without any capture after start-up."""
         if not self.use_graphs:
             return
-        todo = [(r, p) for r in (sizes or self.graph_sizes) for p in variants
-                if (r if p else (r, "norm")) not in self._graphs]
-        for r, project in todo:
+        todo = [(r, p, False) for r in (sizes or self.graph_sizes) for p in variants]
+        if min_p and self.stage.has_head and True in variants:
+            todo += [(r, True, True) for r in (sizes or self.graph_sizes)]
+        todo = [t for t in todo if self._graph_key(*t) not in self._graphs]
+        plan_none = StepPlan(0, 0, [], [])
+        for r, project, with_min_p in todo:
             self.staging.acquire()
             h = self.staging.h
             h["seq_lens"][:r] = 0
@@ -547,6 +652,10 @@ class StageExecutor:
             h["top_p"][:r] = 1
             h["seeds"][:r] = 0
             h["sample_pos"][:r] = 0
+            if self.pen_table is not None:
+                stage_penalties(self.staging, plan_none, 0, r)
+            if with_min_p:
+                stage_min_p(self.staging, plan_none, 0, r)
             for k, n in (("seq_lens", r), ("slot_mapping", r), ("positions", r), ("block_tables", r),
                          ("q_start", r + 1), ("tokens", r), ("temperature", r), ("top_k", r),
                          ("top_p", r), ("seeds", r), ("sample_pos", r)):
@@ -554,7 +663,7 @@ class StageExecutor:
             self.staging.release()
             if self._hidden_in is not None:
                 self._hidden_in[:r].zero_()
-            self._capture(r, project)
+            self._capture(r, project, with_min_p)
         torch.cuda.synchronize()
 
 

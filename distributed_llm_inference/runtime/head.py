@@ -30,7 +30,7 @@ import torch
 from .. import ops
 from ..models.embed_head import LMHead
 from ..utils.cuda import capture_guard, prime_graph_rng
-from .executor import StepPlan, _Staging, _fill_pos
+from .executor import StepPlan, _Staging, _fill_pos, stage_min_p
 from .streams import token_ring
 from .watchdog import TRACKER
 
@@ -50,6 +50,8 @@ class HeadPolicy:
         if not self.enabled or not plan.seq_ids:
             return last
         B = len(plan.seq_ids)
+        if plan.penalised:
+            return last   # the penalty table lives on the last stage alone (min_p still rotates)
         if plan.is_decode and len(plan.sample_rows) == B and B <= self.max_rows:
             return plan.step % self.world
         return last
@@ -87,7 +89,7 @@ class HeadRunner:
             return B
         return self.graph_sizes[bisect.bisect_left(self.graph_sizes, B)]
 
-    def _stage(self, plan: StepPlan, rows: int) -> None:
+    def _stage(self, plan: StepPlan, rows: int, min_p: bool = False) -> None:
         st = self.staging
         st.acquire()
         h = st.h
@@ -104,17 +106,20 @@ class HeadRunner:
             h["seeds"][B:rows] = 0
             h["sample_pos"][B:rows] = 0
         h["step"][0] = plan.step
+        if plan.uses_min_p or min_p:
+            stage_min_p(st, plan, B, rows)
         for k in ("temperature", "top_k", "top_p", "seeds", "sample_pos"):
             st.upload(k, rows)
         st.upload("step", 1)
         st.release()
 
-    def _forward(self, rows: int) -> torch.Tensor:
+    def _forward(self, rows: int, min_p: bool = False) -> torch.Tensor:
         d = self.staging.d
         logits = self.head.project(self.x[:rows], tile=True)
         return ops.sample(logits, temperature=d["temperature"][:rows], top_k=d["top_k"][:rows],
                           top_p=d["top_p"][:rows], seeds=d["seeds"][:rows], step=d["step"],
-                          out=self.out[:rows], counters=d["sample_pos"][:rows])
+                          out=self.out[:rows], counters=d["sample_pos"][:rows],
+                          min_p=d["min_p"][:rows] if min_p else None)
 
     @torch.inference_mode()
     def run(self, plan: StepPlan, x: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -129,37 +134,44 @@ class HeadRunner:
             self.x[:B].copy_(x[:B], non_blocking=True)
         if rows > B:
             self.x[B:rows].zero_()
+        if plan.penalised:
+            raise ValueError("penalised rows sample on the stage that owns the penalty table")
+        min_p = plan.uses_min_p
         if not self.use_graphs:
-            return self._forward(rows)[:B]
-        g = self._graphs.get(rows)
+            return self._forward(rows, min_p)[:B]
+        # a step with a min-p row replays the bucket's min-p variant (both sets are captured by
+        # warmup, before any traffic)
+        g = self._graphs.get((rows, "min_p") if min_p else rows)
         if g is None:
-            g = self._capture(rows)
+            g = self._capture(rows, min_p)
         g.replay()
         return self.out[:B]
 
     @torch.inference_mode()
     def warmup(self) -> None:
-        """Capture every bucket's graph now (dummy greedy rows), before any traffic."""
+        """Capture every bucket's graph now (dummy greedy rows), before any traffic: the plain
+        one and the variant whose sampler applies min-p."""
         if not self.use_graphs:
             return
         for rows in self.graph_sizes:
-            if rows in self._graphs:
-                continue
-            self.x[:rows].zero_()
-            plan = StepPlan(0, 0, list(range(rows)), [1] * rows, sample_rows=list(range(rows)),
-                            temperature=[0.0] * rows, top_k=[0] * rows, top_p=[1.0] * rows,
-                            seeds=[0] * rows)
-            self._stage(plan, rows)
-            self._capture(rows)
+            for min_p in (False, True):
+                if ((rows, "min_p") if min_p else rows) in self._graphs:
+                    continue
+                self.x[:rows].zero_()
+                plan = StepPlan(0, 0, list(range(rows)), [1] * rows,
+                                sample_rows=list(range(rows)), temperature=[0.0] * rows,
+                                top_k=[0] * rows, top_p=[1.0] * rows, seeds=[0] * rows)
+                self._stage(plan, rows, min_p)   # (min-p zeros for the variant that reads them)
+                self._capture(rows, min_p)
         torch.cuda.synchronize(self.device)
 
-    def _capture(self, rows: int):
+    def _capture(self, rows: int, min_p: bool = False):
         cur = torch.cuda.current_stream()
         s = self.capture_stream or torch.cuda.Stream()
         s.wait_stream(cur)
         with torch.cuda.stream(s):
             for _ in range(2):
-                self._forward(rows)
+                self._forward(rows, min_p)
         cur.wait_stream(s)
         prime_graph_rng(torch.cuda.current_device())
         g = torch.cuda.CUDAGraph()
@@ -168,9 +180,9 @@ class HeadRunner:
         # thread_local: publisher threads may synchronise events while this captures
         with capture_guard(), torch.cuda.graph(g, pool=self._pool, stream=s,
                                                capture_error_mode="thread_local"):
-            self._forward(rows)
+            self._forward(rows, min_p)
         cur.wait_stream(s)
-        self._graphs[rows] = g
+        self._graphs[(rows, "min_p") if min_p else rows] = g
         log.info("captured head graph rows=%d", rows)
         return g
 

@@ -20,6 +20,15 @@ for recompute - its prompt and the tokens it already generated are prefilled aga
 sampling (keyed by seed and position) continues exactly where it stopped.  Every stage runs the
 identical block-manager call sequence, so stage-local block tables agree without being
 communicated.
+
+Penalty slots: a request with a repetition / presence / frequency penalty owns one row of the
+sampling rank's penalty table while it runs.  The free list (one for all micro-batches) lives
+here; a sequence takes a slot at admission (none free: it waits at the head of the queue, like a
+KV shortage) and gives it back on retire, abort and preempt.  The row is reset when the slot is
+next assigned, never on release: the stale step of a preempted sequence, possibly still in
+flight, then writes into a released slot harmlessly.  The plan carries the tokens that enter the
+cache as prefill chunks of such sequences (``pen_feed``): the sampling rank sees no prompt
+otherwise.  Tokens sampled while the slot is held are counted on the device by the sampler.
 """
 from __future__ import annotations
 
@@ -34,7 +43,7 @@ class Scheduler:
     def __init__(self, num_micro_batches: int, max_seqs_per_mb: int, max_tokens_per_step: int,
                  blocks_for: Callable[[int], int], total_blocks: int,
                  eos_token_id: Optional[int] = None, max_seq_len: int = 8192,
-                 watermark: Optional[int] = None):
+                 watermark: Optional[int] = None, penalty_slots: int = 0):
         self.M = max(1, num_micro_batches)
         self.max_seqs = max_seqs_per_mb
         self.max_tokens = max_tokens_per_step
@@ -59,6 +68,9 @@ class Scheduler:
         # per micro-batch: ids preempted while a plan holding them was in flight (their tokens
         # from that plan are stale, even if they were re-admitted meanwhile)
         self._stale: List[set] = [set() for _ in range(self.M)]
+        self.penalty_slots = int(penalty_slots)
+        self._free_slots: List[int] = list(range(self.penalty_slots - 1, -1, -1))
+        self.max_slots_held = 0
         self.preemptions = 0
         self.max_running = 0
         self.step = 0
@@ -79,6 +91,9 @@ class Scheduler:
             raise ValueError(f"prompt + max_tokens = {total} exceeds max_seq_len {self.max_seq_len}")
         if self.blocks_for(total) > self.total_blocks:
             raise ValueError("request can never fit in the KV cache")
+        if seq.params.has_penalty and self.penalty_slots <= 0:
+            raise ValueError("repetition / presence / frequency penalties need a penalty table: "
+                             "set ServeConfig.penalty_slots (--penalty-slots) above 0")
         self.waiting.append(seq)
 
     def abort(self, seq_id: int) -> None:
@@ -124,6 +139,13 @@ class Scheduler:
             room = self.total_blocks - (self.watermark if self.num_running() else 0)
             if self.reserved_blocks + need > room:
                 break
+            if s.params.has_penalty:
+                if not self._free_slots:
+                    break   # every penalty slot is held: wait, like a KV shortage
+                s.pen_slot = self._free_slots.pop()
+                s.pen_base, s.pen_fed = s.total_len, 0
+                self.max_slots_held = max(self.max_slots_held,
+                                          self.penalty_slots - len(self._free_slots))
             self.waiting.popleft()
             self.reserved_blocks += need
             self._reserve[s.seq_id] = need
@@ -149,6 +171,7 @@ class Scheduler:
         self.reserved_blocks -= self._reserve.pop(v.seq_id, 0)
         self._order.pop(v.seq_id, None)
         self.pending_free[mb].append(v.seq_id)
+        self._release_slot(v)
         v.status = SeqStatus.WAITING
         v.num_computed = 0
         v.micro_batch = -1
@@ -171,6 +194,36 @@ class Scheduler:
                 self._preempt(mb, victim)
                 if victim is s:
                     break
+
+    def _release_slot(self, s: Sequence) -> None:
+        """Give ``s``'s penalty slot back (its row is reset when the slot is next assigned)."""
+        if s.pen_slot >= 0:
+            self._free_slots.append(s.pen_slot)
+            s.pen_slot = -1
+
+    def _feed(self, s: Sequence, take: int, segs: List[List[int]], toks: List[int]) -> None:
+        """Penalty-table segments for the ``take`` tokens of ``s`` entering the cache: those
+        known when the slot was taken and not fed yet - the prompt as kind 0, earlier outputs (a
+        preempted sequence recomputing) as kind 1; the first segment resets the slot's row."""
+        lo = max(s.num_computed, s.pen_fed)
+        hi = min(s.num_computed + take, s.pen_base)
+        if lo >= hi:
+            return
+        P = len(s.prompt)
+        reset = 1 if s.pen_fed == 0 else 0
+        alltok = s.all_tokens
+        for kind, a, b in ((0, lo, min(hi, P)), (1, max(lo, P), hi)):
+            if a < b:
+                segs.append([s.pen_slot, kind, reset, b - a])
+                toks.extend(alltok[a:b])
+                reset = 0
+        s.pen_fed = hi
+
+    @staticmethod
+    def _sample_controls(s: Sequence):
+        p = s.params
+        return (float(p.min_p), int(s.pen_slot), float(p.repetition_penalty),
+                float(p.presence_penalty), float(p.frequency_penalty))
 
     @staticmethod
     def _decoding(s: Sequence) -> bool:
@@ -219,9 +272,13 @@ class Scheduler:
         self._grow(mb, [(s, take) for s, take, _ in work])
         seq_ids, q_lens, tokens, sample_rows = [], [], [], []
         temps, topk, topp, seeds, spos = [], [], [], [], []
+        ctl: List[tuple] = []                       # per sample row: min_p, slot, rep, pres, freq
+        feed, feed_toks = [], []
         for s, take, pend in work:
             if s.status is not SeqStatus.RUNNING:
                 continue   # preempted to make room
+            if s.pen_slot >= 0:
+                self._feed(s, take, feed, feed_toks)
             row = len(seq_ids)
             seq_ids.append(s.seq_id)
             q_lens.append(take)
@@ -233,13 +290,23 @@ class Scheduler:
                 topp.append(float(s.params.top_p))
                 seeds.append(int(s.seed))
                 spos.append(s.num_computed + take)   # the sampled token's position
+                ctl.append(self._sample_controls(s))
         free_ids = self.pending_free[mb]
         self.pending_free[mb] = []
         if not seq_ids and not free_ids:
             return None
+        # the control lists stay empty (= off) unless some row uses them: plans of requests
+        # without them are what they were before these controls existed
+        extra = {}
+        if any(c[0] > 0 for c in ctl):
+            extra["min_p"] = [c[0] for c in ctl]
+        if any(c[1] >= 0 for c in ctl):
+            extra.update(pen_slot=[c[1] for c in ctl], rep=[c[2] for c in ctl],
+                         pres=[c[3] for c in ctl], freq=[c[4] for c in ctl])
         plan = StepPlan(step=self.step, mb=mb, seq_ids=seq_ids, q_lens=q_lens, free_ids=free_ids,
                         sample_rows=sample_rows, temperature=temps, top_k=topk, top_p=topp,
-                        seeds=seeds, sample_pos=spos, tokens=tokens)
+                        seeds=seeds, sample_pos=spos, tokens=tokens, pen_feed=feed,
+                        pen_feed_tokens=feed_toks, **extra)
         self.step += 1
         # the tokens are (about to be) in the cache on every stage
         byid = {s.seq_id: s for s in m}
@@ -253,7 +320,8 @@ class Scheduler:
         if seq_ids and len(rows) == len(m) and all(q == 1 for q in q_lens) \
                 and len(sample_rows) == len(rows):
             self._decode_cache[mb] = dict(seq_ids=seq_ids, q_lens=q_lens, sample_rows=sample_rows,
-                                          temperature=temps, top_k=topk, top_p=topp, seeds=seeds)
+                                          temperature=temps, top_k=topk, top_p=topp, seeds=seeds,
+                                          extra=extra)
             self._dirty[mb] = False
         else:
             self._decode_cache[mb] = None
@@ -281,7 +349,7 @@ class Scheduler:
         plan = StepPlan(step=self.step, mb=mb, seq_ids=c["seq_ids"], q_lens=c["q_lens"],
                         free_ids=[], sample_rows=c["sample_rows"], temperature=c["temperature"],
                         top_k=c["top_k"], top_p=c["top_p"], seeds=c["seeds"],
-                        sample_pos=[s.num_computed for s in rows], tokens=None)
+                        sample_pos=[s.num_computed for s in rows], tokens=None, **c["extra"])
         self.step += 1
         self.lookahead[mb] = plan
         self._headroom[mb] -= 1
@@ -300,7 +368,7 @@ class Scheduler:
                         free_ids=free_ids, sample_rows=c["sample_rows"],
                         temperature=c["temperature"], top_k=c["top_k"], top_p=c["top_p"],
                         seeds=c["seeds"], sample_pos=[s.num_computed for s in rows],
-                        tokens=tokens)
+                        tokens=tokens, **c["extra"])
         self.step += 1
         self.inflight[mb] = plan
         self._headroom[mb] -= 1
@@ -313,6 +381,7 @@ class Scheduler:
         self.pending_free[mb].append(s.seq_id)
         self.reserved_blocks -= self._reserve.pop(s.seq_id, 0)
         self._order.pop(s.seq_id, None)
+        self._release_slot(s)
         self.finished.append(s)
 
     def on_tokens(self, mb: int, tokens: List[int], now: Optional[float] = None) -> List[Sequence]:

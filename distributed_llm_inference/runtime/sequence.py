@@ -20,6 +20,19 @@ class SamplingParams:
     stop_token_ids: Optional[List[int]] = None
     ignore_eos: bool = False
     min_tokens: int = 0
+    # penalties on the logits before the temperature (vLLM / HF semantics; they need
+    # ServeConfig.penalty_slots > 0): repetition over prompt + generated tokens (1 = off),
+    # presence / frequency over generated tokens only (0 = off)
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    # drop tokens whose probability is below min_p x the most likely token's (0 = off)
+    min_p: float = 0.0
+
+    @property
+    def has_penalty(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0)
 
     def __post_init__(self):
         if self.max_tokens < 1:
@@ -28,6 +41,14 @@ class SamplingParams:
             raise ValueError("temperature must be >= 0")
         if not (0 < self.top_p <= 1.0):
             raise ValueError("top_p must be in (0, 1]")
+        if not self.repetition_penalty > 0:
+            raise ValueError("repetition_penalty must be > 0")
+        if not -2.0 <= self.presence_penalty <= 2.0:
+            raise ValueError("presence_penalty must be in [-2, 2]")
+        if not -2.0 <= self.frequency_penalty <= 2.0:
+            raise ValueError("frequency_penalty must be in [-2, 2]")
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("min_p must be in [0, 1]")
 
 
 class SeqStatus(enum.Enum):
@@ -55,6 +76,10 @@ class Sequence:
     first_token_time: Optional[float] = None
     token_times: List[float] = field(default_factory=list)
     seed: int = 0
+    pen_slot: int = -1           # row of the sampling rank's penalty table (-1 = none)
+    pen_base: int = 0            # tokens known when the slot was taken (later ones were counted
+                                 # by the sampler that chose them)
+    pen_fed: int = 0             # of those, the leading ones already fed to the table
 
     def __post_init__(self):
         if not self.prompt:

@@ -2,8 +2,14 @@
 
 Endpoints:
   POST /generate         {"prompt" | "prompt_ids", "max_tokens", "temperature", "top_k", "top_p",
-                          "seed", "stop_token_ids", "ignore_eos", "stream"}
-  POST /v1/completions   minimal OpenAI-compatible completion (non-streaming and SSE streaming)
+                          "min_p", "repetition_penalty", "presence_penalty",
+                          "frequency_penalty", "seed", "stop_token_ids", "ignore_eos", "stream"}
+  POST /v1/completions   minimal OpenAI-compatible completion (non-streaming and SSE streaming);
+                         the same sampling fields, "presence_penalty" / "frequency_penalty"
+                         with OpenAI's meaning
+
+A value outside its range, or a penalty on a server started without penalty slots
+(``--penalty-slots 0``), is answered 400 on both endpoints; ``min_p`` needs no slot.
   GET  /health           liveness + engine stats (503 when the engine loop died)
   GET  /metrics          Prometheus text format
 """
@@ -45,6 +51,9 @@ def build_app(service: EngineService, tokenizer=None, model_name: str = "model",
             return None
         return tokenizer.decode(ids, skip_special_tokens=True)
 
+    def _or(v, default):
+        return default if v is None else v
+
     def _params(body: dict) -> SamplingParams:
         try:
             return SamplingParams(
@@ -52,8 +61,12 @@ def build_app(service: EngineService, tokenizer=None, model_name: str = "model",
                 temperature=float(body.get("temperature", 0.0)),
                 top_k=int(body.get("top_k", 0) or 0), top_p=float(body.get("top_p", 1.0)),
                 seed=body.get("seed"), stop_token_ids=body.get("stop_token_ids"),
-                ignore_eos=bool(body.get("ignore_eos", False)))
-        except ValueError as e:
+                ignore_eos=bool(body.get("ignore_eos", False)),
+                min_p=float(body.get("min_p", 0.0) or 0.0),
+                repetition_penalty=float(_or(body.get("repetition_penalty"), 1.0)),
+                presence_penalty=float(_or(body.get("presence_penalty"), 0.0)),
+                frequency_penalty=float(_or(body.get("frequency_penalty"), 0.0)))
+        except (TypeError, ValueError) as e:
             raise HTTPException(400, str(e))
 
     def _timeout(body: dict) -> Optional[float]:
@@ -118,7 +131,13 @@ def build_app(service: EngineService, tokenizer=None, model_name: str = "model",
     async def completions(body: dict):
         ids = _encode(body)
         params = _params(body)
-        fut, q = service.submit(ids, params, stream=bool(body.get("stream")))
+        try:
+            # as on /generate: what submit refuses (a penalty without penalty slots, and also an
+            # engine that has failed) answers 400.  With pipeline replicas a refusal by a remote
+            # replica's scheduler arrives later, through the future, and is not a 400
+            fut, q = service.submit(ids, params, stream=bool(body.get("stream")))
+        except Exception as e:
+            raise HTTPException(400, str(e))
         if q is not None:
             return StreamingResponse(_stream(q, fut=fut, timeout=_timeout(body)),
                                      media_type="text/event-stream")

@@ -63,6 +63,12 @@ class EngineService:
                stream: bool = False) -> "tuple[Future, Optional[queue.Queue]]":
         if self.error is not None:
             raise RuntimeError(f"engine failed: {self.error!r}")
+        sched = getattr(self.driver, "sched", None)
+        if params.has_penalty and getattr(sched, "penalty_slots", 0) <= 0:
+            # refused here, in the caller's thread (the HTTP front end answers 400), with the
+            # message Scheduler.add would give
+            raise ValueError("repetition / presence / frequency penalties need a penalty table: "
+                             "start the server with --penalty-slots above 0")
         seq = Sequence(list(prompt_ids), params)
         fut: Future = Future()
         fut.seq_id = seq.seq_id  # type: ignore[attr-defined]  (for abort on timeout / disconnect)
