@@ -1166,36 +1166,57 @@ void moe_group(Tensor ids, Tensor expert_count, Tensor expert_offset, Tensor sor
                                  (int)E, (int)k, (int)tb.cap, cur_stream()), "moe_group");
 }
 
+// The routed experts' weights with the scale that goes with them, the format inferred from w's
+// dtype: bf16 [E, N, K] without a scale; fp8 e4m3fn [E, N, K] with w_scale fp32 [E, N] (one per
+// weight row); uint8 MXFP4 nibbles [E, N, K / 2] with w_block_scale uint8 [E, N, K / 32] (e8m0,
+// one per 32 k).  K is the logical reduction length
+struct ExpertArgs {
+  dli::ExpertW w;
+  int64_t E, N, K;
+};
+ExpertArgs check_expert_weights(const char* what, const Tensor& w, const optional<Tensor>& w_scale,
+                                const at::Device& dev) {
+  CHECK_IN(w);
+  if (w_scale.has_value()) { CHECK_IN(*w_scale); }
+  TORCH_CHECK(w.dim() == 3, what, ": w [E, N, K]");
+  const int64_t E = w.size(0), N = w.size(1);
+  if (w.scalar_type() == at::kBFloat16) {
+    TORCH_CHECK(!w_scale.has_value(), what, ": bf16 expert weights take no scale (w_scale goes "
+                "with fp8 e4m3fn weights, w_block_scale with uint8 MXFP4 weights)");
+    return {{w.data_ptr(), nullptr, dli::kExpertBf16}, E, N, w.size(2)};
+  }
+  if (w.scalar_type() == at::kFloat8_e4m3fn) {
+    TORCH_CHECK(w_scale.has_value() && w_scale->scalar_type() == at::kFloat, what,
+                ": fp8 e4m3fn expert weights go with an fp32 w_scale (bf16 expert weights only "
+                "go without a scale)");
+    TORCH_CHECK(w_scale->dim() == 2 && w_scale->size(0) == E && w_scale->size(1) == N &&
+                    w_scale->device() == dev, what, ": w_scale [E, N] on the weights' device");
+    return {{w.data_ptr(), w_scale->data_ptr(), dli::kExpertFp8}, E, N, w.size(2)};
+  }
+  TORCH_CHECK(w.scalar_type() == at::kByte, what, ": bf16 weights, fp8 e4m3fn weights with "
+              "w_scale, or uint8 MXFP4 weights with w_block_scale");
+  const int64_t K = 2 * w.size(2);
+  TORCH_CHECK(w_scale.has_value() && w_scale->scalar_type() == at::kByte, what,
+              ": uint8 MXFP4 expert weights go with a uint8 w_block_scale (an fp32 w_scale goes "
+              "with fp8 e4m3fn weights)");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, what, ": needs K % 128 == 0");
+  TORCH_CHECK(w_scale->dim() == 3 && w_scale->size(0) == E && w_scale->size(1) == N &&
+                  w_scale->size(2) == K / 32 && w_scale->device() == dev,
+              what, ": w_block_scale [E, N, K / 32] on the weights' device");
+  return {{w.data_ptr(), w_scale->data_ptr(), dli::kExpertFp4}, E, N, K};
+}
+
 // epilogue 0: out h [>= P, I] = swiglu(x[token] . W[e]^T), x [T, K], W [E, 2 I, K];
 // epilogue 1: out y [>= P, N] (row = pair index) = x[start + r] . W[e]^T, x = h [>= P, K], W [E, N, K]
-// W is bf16, or with w_scale [E, N] (fp32, one per weight row) fp8 e4m3fn, or with w_block_scale
-// [E, N, K / 32] (e8m0 bytes, one per 32 k) MXFP4 nibbles uint8 [E, N, K / 2]
 void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor tile_expert,
                       Tensor tile_start, Tensor tile_rows, Tensor n_tiles, int64_t T, int64_t k,
-                      int64_t epilogue, optional<Tensor> w_scale,
-                      optional<Tensor> w_block_scale) {
-  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
+                      int64_t epilogue, optional<Tensor> scale) {
+  CHECK_IN(out); CHECK_IN(x);
   CHECK_BF16(out); CHECK_BF16(x);
-  const bool fp8 = w_scale.has_value();
-  const bool fp4 = w_block_scale.has_value();
-  TORCH_CHECK(!(fp8 && fp4), "moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both");
-  if (fp4) {
-    CHECK_IN(*w_block_scale);
-    TORCH_CHECK(w.scalar_type() == at::kByte && w_block_scale->scalar_type() == at::kByte,
-                "moe_grouped_gemm: w_block_scale (uint8) goes with uint8 MXFP4 weights");
-  } else if (fp8) {
-    CHECK_IN(*w_scale); CHECK_F32(*w_scale);
-    TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn,
-                "moe_grouped_gemm: w_scale goes with fp8 e4m3fn weights");
-  } else {
-    TORCH_CHECK(w.scalar_type() == at::kBFloat16,
-                "moe_grouped_gemm: bf16 weights, fp8 e4m3fn weights with w_scale, or uint8 MXFP4 "
-                "weights with w_block_scale");
-  }
-  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
-              "moe_grouped_gemm: out / x 2-D, w [E, N, K]");
+  const ExpertArgs e = check_expert_weights("moe_grouped_gemm", w, scale, x.device());
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2, "moe_grouped_gemm: out / x 2-D");
   TORCH_CHECK(epilogue == 0 || epilogue == 1, "moe_grouped_gemm: epilogue 0 (gate|up) or 1 (down)");
-  const int64_t E = w.size(0), N = w.size(1), K = fp4 ? 2 * w.size(2) : w.size(2);
+  const int64_t E = e.E, N = e.N, K = e.K;
   const MoeTables tb = check_moe_tables(sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles,
                                         T, E, k, x.device(), "moe_grouped_gemm");
   TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "moe_grouped_gemm: needs K % 128 == 0");
@@ -1207,32 +1228,7 @@ void moe_grouped_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tenso
   TORCH_CHECK(out.device() == x.device() && w.device() == x.device(),
               "moe_grouped_gemm: one device");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  if (fp4) {
-    TORCH_CHECK(w_block_scale->dim() == 3 && w_block_scale->size(0) == E &&
-                    w_block_scale->size(1) == N && w_block_scale->size(2) == K / 32 &&
-                    w_block_scale->device() == x.device(),
-                "moe_grouped_gemm: w_block_scale [E, N, K / 32] on the weights' device");
-    check_rc(dli::launch_moe_grouped_gemm_fp4(
-                 bp(out), bp(x), w.data_ptr<uint8_t>(), w_block_scale->data_ptr<uint8_t>(),
-                 sorted_pairs.data_ptr<int>(), tile_expert.data_ptr<int>(),
-                 tile_start.data_ptr<int>(), tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(),
-                 (int)tb.cap, (int)T, (int)E, (int)k, (int)N, (int)K, (int)epilogue, cur_stream()),
-             "moe_grouped_gemm");
-    return;
-  }
-  if (fp8) {
-    TORCH_CHECK(w_scale->dim() == 2 && w_scale->size(0) == E && w_scale->size(1) == N &&
-                    w_scale->device() == x.device(),
-                "moe_grouped_gemm: w_scale [E, N] on the weights' device");
-    check_rc(dli::launch_moe_grouped_gemm_fp8(
-                 bp(out), bp(x), static_cast<const uint8_t*>(w.data_ptr()),
-                 w_scale->data_ptr<float>(), sorted_pairs.data_ptr<int>(),
-                 tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
-                 tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(), (int)tb.cap, (int)T, (int)E,
-                 (int)k, (int)N, (int)K, (int)epilogue, cur_stream()), "moe_grouped_gemm");
-    return;
-  }
-  check_rc(dli::launch_moe_grouped_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
+  check_rc(dli::launch_moe_grouped_gemm(bp(out), bp(x), e.w, sorted_pairs.data_ptr<int>(),
                                         tile_expert.data_ptr<int>(), tile_start.data_ptr<int>(),
                                         tile_rows.data_ptr<int>(), n_tiles.data_ptr<int>(),
                                         (int)tb.cap, (int)T, (int)E, (int)k, (int)N, (int)K,
@@ -1267,83 +1263,24 @@ int64_t check_moe_tile(const char* what, const Tensor& out, const Tensor& x, con
   return E;
 }
 
-// moe_grouped_gemm's products for bf16 W on the tile kernel (moe_tile.hip): 128-row tiles derived
-// in the kernel from expert_count [E] / expert_offset [E + 1]; N % 128 == 0, K % 64 == 0
+// moe_grouped_gemm's products on the tile kernel (moe_tile.hip): 128-row tiles derived in the
+// kernel from expert_count [E] / expert_offset [E + 1]; N % 128 == 0, K % 64 == 0 (MXFP4: K % 128)
 void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor expert_count,
-                   Tensor expert_offset, int64_t T, int64_t k, int64_t epilogue) {
-  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w);
+                   Tensor expert_offset, int64_t T, int64_t k, int64_t epilogue,
+                   optional<Tensor> scale) {
+  CHECK_IN(out); CHECK_IN(x);
   CHECK_BF16(out); CHECK_BF16(x);
   CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
   CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
-  TORCH_CHECK(w.scalar_type() == at::kBFloat16,
-              "moe_tile_gemm: bf16 expert weights only (fp8 / MXFP4 experts run on "
-              "moe_grouped_gemm)");
-  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w.dim() == 3,
-              "moe_tile_gemm: out / x 2-D, w [E, N, K]");
-  const int64_t N = w.size(1), K = w.size(2);
-  const int64_t E = check_moe_tile("moe_tile_gemm", out, x, w, sorted_pairs, expert_count,
-                                   expert_offset, T, k, epilogue, K);
+  const ExpertArgs e = check_expert_weights("moe_tile_gemm", w, scale, x.device());
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2, "moe_tile_gemm: out / x 2-D");
+  check_moe_tile("moe_tile_gemm", out, x, w, sorted_pairs, expert_count, expert_offset, T, k,
+                 epilogue, e.K);
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  check_rc(dli::launch_moe_tile_gemm(bp(out), bp(x), bp(w), sorted_pairs.data_ptr<int>(),
+  check_rc(dli::launch_moe_tile_gemm(bp(out), bp(x), e.w, sorted_pairs.data_ptr<int>(),
                                      expert_count.data_ptr<int>(), expert_offset.data_ptr<int>(),
-                                     (int)T, (int)E, (int)k, (int)N, (int)K, (int)epilogue,
+                                     (int)T, (int)e.E, (int)k, (int)e.N, (int)e.K, (int)epilogue,
                                      cur_stream()), "moe_tile_gemm");
-}
-
-// the same on fp8 experts: w8 [E, N, K] e4m3fn, w_scale [E, N] fp32 (one per weight row, applied
-// to the fp32 accumulator); the activations stay bf16
-void moe_tile_gemm_fp8(Tensor out, Tensor x, Tensor w8, Tensor w_scale, Tensor sorted_pairs,
-                       Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
-                       int64_t epilogue) {
-  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w8); CHECK_IN(w_scale);
-  CHECK_BF16(out); CHECK_BF16(x);
-  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
-  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
-  TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn && w_scale.scalar_type() == at::kFloat,
-              "moe_tile_gemm_fp8: fp8 e4m3fn expert weights with fp32 w_scale");
-  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w8.dim() == 3,
-              "moe_tile_gemm_fp8: out / x 2-D, w8 [E, N, K]");
-  const int64_t N = w8.size(1), K = w8.size(2);
-  const int64_t E = check_moe_tile("moe_tile_gemm_fp8", out, x, w8, sorted_pairs, expert_count,
-                                   expert_offset, T, k, epilogue, K);
-  TORCH_CHECK(w_scale.dim() == 2 && w_scale.size(0) == E && w_scale.size(1) == N &&
-                  w_scale.device() == x.device(),
-              "moe_tile_gemm_fp8: w_scale [E, N] on the weights' device");
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  check_rc(dli::launch_moe_tile_gemm_fp8(
-               bp(out), bp(x), static_cast<const uint8_t*>(w8.data_ptr()),
-               w_scale.data_ptr<float>(), sorted_pairs.data_ptr<int>(),
-               expert_count.data_ptr<int>(), expert_offset.data_ptr<int>(), (int)T, (int)E,
-               (int)k, (int)N, (int)K, (int)epilogue, cur_stream()), "moe_tile_gemm_fp8");
-}
-
-// the same on MXFP4 experts: w4 uint8 [E, N, K / 2] nibbles, w_block_scale uint8 [E, N, K / 32]
-// e8m0 bytes spent in the exact widening to bf16; K % 128 == 0
-void moe_tile_gemm_fp4(Tensor out, Tensor x, Tensor w4, Tensor w_block_scale,
-                       Tensor sorted_pairs, Tensor expert_count, Tensor expert_offset, int64_t T,
-                       int64_t k, int64_t epilogue) {
-  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w4); CHECK_IN(w_block_scale);
-  CHECK_BF16(out); CHECK_BF16(x);
-  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
-  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
-  TORCH_CHECK(w4.scalar_type() == at::kByte && w_block_scale.scalar_type() == at::kByte,
-              "moe_tile_gemm_fp4: uint8 MXFP4 expert weights with uint8 w_block_scale");
-  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && w4.dim() == 3,
-              "moe_tile_gemm_fp4: out / x 2-D, w4 [E, N, K / 2]");
-  const int64_t N = w4.size(1), K = 2 * w4.size(2);
-  TORCH_CHECK(K >= 128 && K % 128 == 0, "moe_tile_gemm_fp4: needs K % 128 == 0");
-  const int64_t E = check_moe_tile("moe_tile_gemm_fp4", out, x, w4, sorted_pairs, expert_count,
-                                   expert_offset, T, k, epilogue, K);
-  TORCH_CHECK(w_block_scale.dim() == 3 && w_block_scale.size(0) == E &&
-                  w_block_scale.size(1) == N && w_block_scale.size(2) == K / 32 &&
-                  w_block_scale.device() == x.device(),
-              "moe_tile_gemm_fp4: w_block_scale [E, N, K / 32] on the weights' device");
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  check_rc(dli::launch_moe_tile_gemm_fp4(
-               bp(out), bp(x), w4.data_ptr<uint8_t>(), w_block_scale.data_ptr<uint8_t>(),
-               sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
-               expert_offset.data_ptr<int>(), (int)T, (int)E, (int)k, (int)N, (int)K,
-               (int)epilogue, cur_stream()), "moe_tile_gemm_fp4");
 }
 
 // shared [T, H] (bf16) with shared_w [T] (fp32): the shared expert's term, added after the slots
@@ -1643,24 +1580,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped weight-streaming MFMA GEMM over the routed experts (0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("tile_expert"), py::arg("tile_start"), py::arg("tile_rows"), py::arg("n_tiles"),
-        py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("w_scale") = py::none(),
-        py::arg("w_block_scale") = py::none());
+        py::arg("T"), py::arg("k"), py::arg("epilogue"), py::arg("scale") = py::none());
   m.def("moe_tile_gemm", &moe_tile_gemm,
-        "grouped MFMA tile GEMM over the routed bf16 experts, <= 128-row tiles (0: gate|up + "
-        "SwiGLU, 1: down)",
+        "grouped MFMA tile GEMM over the routed experts, <= 128-row tiles (0: gate|up + SwiGLU, "
+        "1: down)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
-        py::arg("epilogue"));
-  m.def("moe_tile_gemm_fp8", &moe_tile_gemm_fp8,
-        "the tile GEMM over fp8 e4m3fn experts with fp32 row scales [E, N]",
-        py::arg("out"), py::arg("x"), py::arg("w8"), py::arg("w_scale"), py::arg("sorted_pairs"),
-        py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
-        py::arg("epilogue"));
-  m.def("moe_tile_gemm_fp4", &moe_tile_gemm_fp4,
-        "the tile GEMM over MXFP4 experts [E, N, K / 2] with e8m0 block scales [E, N, K / 32]",
-        py::arg("out"), py::arg("x"), py::arg("w4"), py::arg("w_block_scale"),
-        py::arg("sorted_pairs"), py::arg("expert_count"), py::arg("expert_offset"),
-        py::arg("T"), py::arg("k"), py::arg("epilogue"));
+        py::arg("epilogue"), py::arg("scale") = py::none());
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"), py::arg("shared") = py::none(),
         py::arg("shared_w") = py::none());

@@ -212,51 +212,40 @@ int launch_moe_topk_shared(int* ids, float* w, float* shared_w, const bf16* logi
 int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int* sorted_pairs,
                      int* tile_expert, int* tile_start, int* tile_rows, int* n_tiles, int T, int E,
                      int k, int cap, hipStream_t stream);
-// W [E, N, K], N % 32 == 0, K % 128 == 0.  epilogue 0 (gate|up): x [T, K] gathered by
-// sorted_pairs / k, W rows swiglu_interleave'd, out h [P, N / 2]; 1 (down): x = h [P, K], out
-// y [P, N] with tile row r at row sorted_pairs[start + r]
-int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+// The routed experts' weights in one of three formats (`format` is an ExpertFormat):
+//   bf16:  w [E, N, K] bf16, scale null;
+//   fp8:   w [E, N, K] e4m3fn bytes, scale [E, N] fp32 (one per weight row, in the rows' stored
+//          order), applied to the fp32 accumulator;
+//   MXFP4: w [E, N, K / 2] e2m1 nibbles (element 2 j in the low nibble of byte j), scale
+//          [E, N, K / 32] e8m0 bytes (one per 32 k of a stored weight row), spent in the exact
+//          widening to bf16: no epilogue scale.
+// The activations stay bf16.  A quantised format with a null scale is -5, an unknown format -6.
+enum ExpertFormat { kExpertBf16 = 0, kExpertFp8 = 1, kExpertFp4 = 2 };
+struct ExpertW {
+  const void* w;
+  const void* scale;
+  int format;
+};
+// N % 32 == 0, K % 128 == 0.  epilogue 0 (gate|up): x [T, K] gathered by sorted_pairs / k, W rows
+// swiglu_interleave'd, out h [P, N / 2]; 1 (down): x = h [P, K], out y [P, N] with tile row r at
+// row sorted_pairs[start + r]
+int launch_moe_grouped_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                             const int* tile_expert, const int* tile_start, const int* tile_rows,
                             const int* n_tiles, int cap, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream);
-// the same on fp8 weights: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32 (one per weight row, in
-// the rows' stored order), applied to the fp32 accumulator; the activations stay bf16
-int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
-                                const int* sorted_pairs, const int* tile_expert,
-                                const int* tile_start, const int* tile_rows, const int* n_tiles,
-                                int cap, int T, int E, int k, int N, int K, int epilogue,
-                                hipStream_t stream);
-// the same on MXFP4 weights: W4 [E, N, K / 2] e2m1 nibbles (element 2 j in the low nibble of byte
-// j), bscale [E, N, K / 32] e8m0 bytes (one per 32 k of a stored weight row), spent in the exact
-// widening to bf16: no epilogue scale; the activations stay bf16
-int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
-                                const int* sorted_pairs, const int* tile_expert,
-                                const int* tile_start, const int* tile_rows, const int* n_tiles,
-                                int cap, int T, int E, int k, int N, int K, int epilogue,
-                                hipStream_t stream);
 // Grouped MFMA tile GEMM for experts with many rows (moe_tile.hip): the products of
-// launch_moe_grouped_gemm (bf16 W [E, N, K], the same two epilogues, x and out as there) on tiles
-// of <= 128 rows x 128 weight rows staged in LDS; N % 128 == 0, K % 64 == 0.  The 128-row tiles
-// are derived in the kernel from expert_count [E] / expert_offset [E + 1] (launch_moe_group's);
-// the grid is (N / 128, moe_tile_gemm_capacity) = min(E, P) + P / 128 row tiles
+// launch_moe_grouped_gemm (the same two epilogues, x and out as there) on tiles of <= 128 rows x
+// 128 weight rows staged in LDS; N % 128 == 0, K % 64 == 0 (MXFP4: K % 128 == 0).  The 128-row
+// tiles are derived in the kernel from expert_count [E] / expert_offset [E + 1]
+// (launch_moe_group's); the grid is (N / 128, moe_tile_gemm_capacity) = min(E, P) + P / 128 row
+// tiles.  Quantised bytes are staged in LDS and widened exactly to bf16 when a fragment is read,
+// so the MFMAs and their order are the bf16 experts'; fp8: gate and up are each scaled by their
+// own row's scale before their bf16 rounding; MXFP4: the bf16 result on the dequantised weights,
+// bit for bit
 int moe_tile_gemm_capacity(int T, int E, int k);
-int launch_moe_tile_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+int launch_moe_tile_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                          const int* expert_count, const int* expert_offset, int T, int E, int k,
                          int N, int K, int epilogue, hipStream_t stream);
-// the same tiles on quantised experts: the quantised bytes are staged in LDS and widened exactly
-// to bf16 when a fragment is read, so the MFMAs and their order are launch_moe_tile_gemm's.
-// fp8: W8 [E, N, K] e4m3fn bytes, w_scale [E, N] fp32 applied to the fp32 accumulator (gate and
-// up each by their own row's scale before their bf16 rounding).  MXFP4: W4 [E, N, K / 2] nibbles,
-// bscale [E, N, K / 32] e8m0 bytes spent in the widening, K % 128 == 0: the bf16 kernel's result
-// on the dequantised weights, bit for bit.  The scale pointers must not be null (-5)
-int launch_moe_tile_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
-                             const int* sorted_pairs, const int* expert_count,
-                             const int* expert_offset, int T, int E, int k, int N, int K,
-                             int epilogue, hipStream_t stream);
-int launch_moe_tile_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
-                             const int* sorted_pairs, const int* expert_count,
-                             const int* expert_offset, int T, int E, int k, int N, int K,
-                             int epilogue, hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

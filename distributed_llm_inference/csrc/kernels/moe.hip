@@ -428,30 +428,23 @@ int launch_grouped(bf16* out, const bf16* x, const void* W, const void* wscale,
 
 }  // namespace
 
-int launch_moe_grouped_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+int launch_moe_grouped_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                             const int* tile_expert, const int* tile_start, const int* tile_rows,
                             const int* n_tiles, int cap, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream) {
-  return launch_grouped<kMoeBf16>(out, x, W, nullptr, sorted_pairs, tile_expert, tile_start,
-                                  tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
-}
-
-int launch_moe_grouped_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
-                                const int* sorted_pairs, const int* tile_expert,
-                                const int* tile_start, const int* tile_rows, const int* n_tiles,
-                                int cap, int T, int E, int k, int N, int K, int epilogue,
-                                hipStream_t stream) {
-  return launch_grouped<kMoeFp8>(out, x, W8, w_scale, sorted_pairs, tile_expert, tile_start,
-                                 tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
-}
-
-int launch_moe_grouped_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
-                                const int* sorted_pairs, const int* tile_expert,
-                                const int* tile_start, const int* tile_rows, const int* n_tiles,
-                                int cap, int T, int E, int k, int N, int K, int epilogue,
-                                hipStream_t stream) {
-  return launch_grouped<kMoeFp4>(out, x, W4, bscale, sorted_pairs, tile_expert, tile_start,
-                                 tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+  static_assert(kMoeBf16 == kExpertBf16 && kMoeFp8 == kExpertFp8 && kMoeFp4 == kExpertFp4);
+  switch (W.format) {
+    case kExpertBf16:
+      return launch_grouped<kMoeBf16>(out, x, W.w, nullptr, sorted_pairs, tile_expert, tile_start,
+                                      tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+    case kExpertFp8:
+      return launch_grouped<kMoeFp8>(out, x, W.w, W.scale, sorted_pairs, tile_expert, tile_start,
+                                     tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+    case kExpertFp4:
+      return launch_grouped<kMoeFp4>(out, x, W.w, W.scale, sorted_pairs, tile_expert, tile_start,
+                                     tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+  }
+  return -6;
 }
 
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,

@@ -365,27 +365,22 @@ int launch_tile(bf16* out, const bf16* x, const void* W, const void* wscale,
 
 }  // namespace
 
-int launch_moe_tile_gemm(bf16* out, const bf16* x, const bf16* W, const int* sorted_pairs,
+int launch_moe_tile_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                          const int* expert_count, const int* expert_offset, int T, int E, int k,
                          int N, int K, int epilogue, hipStream_t stream) {
-  return launch_tile<kTileBf16>(out, x, W, nullptr, sorted_pairs, expert_count, expert_offset, T,
-                                E, k, N, K, epilogue, stream);
-}
-
-int launch_moe_tile_gemm_fp8(bf16* out, const bf16* x, const uint8_t* W8, const float* w_scale,
-                             const int* sorted_pairs, const int* expert_count,
-                             const int* expert_offset, int T, int E, int k, int N, int K,
-                             int epilogue, hipStream_t stream) {
-  return launch_tile<kTileFp8>(out, x, W8, w_scale, sorted_pairs, expert_count, expert_offset, T,
-                               E, k, N, K, epilogue, stream);
-}
-
-int launch_moe_tile_gemm_fp4(bf16* out, const bf16* x, const uint8_t* W4, const uint8_t* bscale,
-                             const int* sorted_pairs, const int* expert_count,
-                             const int* expert_offset, int T, int E, int k, int N, int K,
-                             int epilogue, hipStream_t stream) {
-  return launch_tile<kTileFp4>(out, x, W4, bscale, sorted_pairs, expert_count, expert_offset, T,
-                               E, k, N, K, epilogue, stream);
+  static_assert(kTileBf16 == kExpertBf16 && kTileFp8 == kExpertFp8 && kTileFp4 == kExpertFp4);
+  switch (W.format) {
+    case kExpertBf16:
+      return launch_tile<kTileBf16>(out, x, W.w, nullptr, sorted_pairs, expert_count,
+                                    expert_offset, T, E, k, N, K, epilogue, stream);
+    case kExpertFp8:
+      return launch_tile<kTileFp8>(out, x, W.w, W.scale, sorted_pairs, expert_count,
+                                   expert_offset, T, E, k, N, K, epilogue, stream);
+    case kExpertFp4:
+      return launch_tile<kTileFp4>(out, x, W.w, W.scale, sorted_pairs, expert_count,
+                                   expert_offset, T, E, k, N, K, epilogue, stream);
+  }
+  return -6;
 }
 
 }  // namespace dli

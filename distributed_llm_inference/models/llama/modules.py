@@ -338,45 +338,39 @@ class MoEMLP(nn.Module):
     def is_fp8(self) -> bool:
         return self.w_gate_up_scale is not None
 
-    def quantize_experts_fp8(self) -> None:
-        """Expert weights -> fp8 e4m3 with per-row scales (ops.quantize_expert_weights_fp8: one
-        expert at a time), in place of the bf16 tensors, which are freed.  The scale of a gate|up
-        row travels with the row, so the interleaved order is kept."""
-        if self.is_fp8:
-            return
-        if self.is_mxfp4:
-            raise ValueError("quantize_experts_fp8: the experts are MXFP4 already")
-        for name in ("w_gate_up", "w_down"):
-            w8, scale = ops.quantize_expert_weights_fp8(getattr(self, name).data)
-            setattr(self, name, nn.Parameter(w8, requires_grad=False))
-            setattr(self, name + "_scale", scale)
-
     @property
     def is_mxfp4(self) -> bool:
         return self.w_gate_up_block_scale is not None
 
-    def quantize_experts_mxfp4(self) -> None:
-        """Expert weights -> MXFP4 nibbles with e8m0 block scales
-        (ops.quantize_expert_weights_mxfp4: one expert at a time), in place of the bf16 tensors,
-        which are freed.  A scale belongs to 32 input features of a stored row, so the gate|up
-        rows are quantised in their interleaved order."""
-        if self.is_mxfp4:
-            return
-        if self.is_fp8:
-            raise ValueError("quantize_experts_mxfp4: the experts are fp8 already")
-        for name in ("w_gate_up", "w_down"):
-            packed, scales = ops.quantize_expert_weights_mxfp4(getattr(self, name).data)
-            setattr(self, name, nn.Parameter(packed, requires_grad=False))
-            setattr(self, name + "_block_scale", scales)
+    def experts(self, name: str) -> ops.ExpertWeights:
+        """``w_gate_up`` or ``w_down`` with whichever of its scale buffers is set."""
+        scale = getattr(self, name + "_scale")
+        if scale is None:
+            scale = getattr(self, name + "_block_scale")
+        return ops.ExpertWeights(getattr(self, name), scale)
 
-    def _expert_bf16(self, name: str, e: int) -> torch.Tensor:
-        """Expert e's weight as bf16: the tensor itself, or the dequantised fp8 / MXFP4 rows."""
-        w = getattr(self, name)[e]
-        if self.is_mxfp4:
-            return ops.dequantize_mxfp4(w, getattr(self, name + "_block_scale")[e])
-        if not self.is_fp8:
-            return w
-        return (w.float() * getattr(self, name + "_scale")[e][:, None]).to(torch.bfloat16)
+    def _quantize_experts(self, fmt: str) -> None:
+        """Expert weights -> ``fmt`` (ops.ExpertWeights.quantize: one expert at a time), in place
+        of the bf16 tensors, which are freed.  A scale belongs to a stored gate|up row (MXFP4: to
+        32 input features of it), so the rows are quantised in their interleaved order."""
+        have = "fp8" if self.is_fp8 else "mxfp4" if self.is_mxfp4 else "bf16"
+        if have == fmt:
+            return
+        if have != "bf16":
+            raise ValueError(f"quantize_experts_{fmt}: the experts are "
+                             f"{'MXFP4' if have == 'mxfp4' else have} already")
+        for name in ("w_gate_up", "w_down"):
+            q = ops.ExpertWeights.quantize(getattr(self, name).data, fmt)
+            setattr(self, name, nn.Parameter(q.w, requires_grad=False))
+            setattr(self, name + ("_scale" if fmt == "fp8" else "_block_scale"), q.scale)
+
+    def quantize_experts_fp8(self) -> None:
+        """Expert weights -> fp8 e4m3 with per-row scales."""
+        self._quantize_experts("fp8")
+
+    def quantize_experts_mxfp4(self) -> None:
+        """Expert weights -> MXFP4 nibbles with e8m0 block scales."""
+        self._quantize_experts("mxfp4")
 
     def set_fused_swiglu(self, on: bool) -> None:
         """No-op for the routed experts: the grouped GEMM's only epilogue reads interleaved
@@ -387,15 +381,12 @@ class MoEMLP(nn.Module):
     def forward(self, normed: torch.Tensor, x_q=None, defer_reduce: bool = False, norm=None):
         if x_q is not None or norm is not None:
             raise RuntimeError("MoEMLP takes normalised bf16 rows (the layer's generic body)")
-        if not self.shared_size:
-            return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
-                               self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale,
-                               self.w_gate_up_block_scale, self.w_down_block_scale)
-        shared = self.shared_expert(normed)     # a plain bf16 [T, H]: nothing deferred
-        return ops.moe_mlp(normed, self.gate(normed), self.w_gate_up, self.w_down, self.top_k,
-                           self.norm_topk_prob, self.w_gate_up_scale, self.w_down_scale,
-                           self.w_gate_up_block_scale, self.w_down_block_scale,
-                           num_experts=self.num_experts, shared=shared)
+        # the shared expert's output is a plain bf16 [T, H]: nothing deferred
+        shared = self.shared_expert(normed) if self.shared_size else None
+        return ops.moe_mlp(normed, self.gate(normed), self.experts("w_gate_up"),
+                           self.experts("w_down"), self.top_k, self.norm_topk_prob,
+                           num_experts=self.num_experts if self.shared_size else None,
+                           shared=shared)
 
     # ------------------------------------------------------------------ weights
     def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
@@ -464,9 +455,10 @@ class MoEMLP(nn.Module):
                        pre + "shared_expert.up_proj.weight": up,
                        pre + "shared_expert.down_proj.weight": sh.down_proj.weight})
         I = self.intermediate_size
+        gate_up, down = self.experts("w_gate_up"), self.experts("w_down")
         for e in range(self.num_experts):
-            gate, up = ops.swiglu_deinterleave(self._expert_bf16("w_gate_up", e)).split([I, I], 0)
-            for n, w in zip(names, (gate, up, self._expert_bf16("w_down", e))):
+            gate, up = ops.swiglu_deinterleave(gate_up.dequantize(e)).split([I, I], 0)
+            for n, w in zip(names, (gate, up, down.dequantize(e))):
                 sd[f"{pre}experts.{e}.{n}.weight"] = w
         return sd
 

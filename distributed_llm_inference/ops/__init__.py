@@ -1421,6 +1421,7 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
 
 # ----------------------------------------------------------------------------- sparse MoE
 MoERouting = ref.MoERouting
+ExpertWeights = ref.ExpertWeights
 MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
 MOE_MAX_TOPK = ref.MOE_MAX_TOPK
 moe_tile_capacity = ref.moe_tile_capacity
@@ -1495,13 +1496,7 @@ def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
     return bool(rows and torch.device(device).type == "cuda" and T * k >= rows * E)
 
 
-def _moe_weight_format(w: torch.Tensor, w_scale, w_block_scale) -> str:
-    if w_block_scale is not None or w.dtype == torch.uint8:
-        return "mxfp4"
-    return "bf16" if w_scale is None and w.dtype == torch.bfloat16 else "fp8"
-
-
-def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool = False,
+def moe_grouped_gemm(x: torch.Tensor, w, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
                      w_scale: Optional[torch.Tensor] = None,
                      w_block_scale: Optional[torch.Tensor] = None,
@@ -1515,7 +1510,8 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     e4m3fn (:func:`quantize_expert_weights_fp8`): the row scale multiplies the fp32 product, the
     activations stay bf16.  With ``w_block_scale [E, N, K / 32]`` (uint8 e8m0) ``w`` is MXFP4
     nibbles ``uint8 [E, N, K / 2]`` (:func:`quantize_expert_weights_mxfp4`), widened exactly to
-    bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights.
+    bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights.  ``w`` may
+    also be an :class:`ExpertWeights`, which carries its scale: then neither keyword is given.
 
     ``tiles``: True runs the grouped MFMA tile GEMM (moe_tile.hip, on the GPU: N % 128 == 0,
     K % 64 == 0; the same products, another K summation order), False the weight-streaming
@@ -1525,27 +1521,29 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     exactly to bf16 and run the bf16 tile kernel's MFMAs in its order: MXFP4 gives its result on
     the dequantised weights bit for bit, fp8 the same up to the row scale applied to the fp32
     sum.  The CPU path ignores ``tiles``."""
+    if isinstance(w, ExpertWeights):
+        if w_scale is not None or w_block_scale is not None:
+            raise ValueError("moe_grouped_gemm: ExpertWeights carry their scale; w_scale / "
+                             "w_block_scale go with a bare weight tensor")
+        e = w
+        blocks = e.scale is not None and e.scale.dtype == torch.uint8
+    else:
+        blocks = w_block_scale is not None
+        if w_scale is not None and (blocks or w.dtype == torch.uint8):
+            raise ValueError("moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both")
+        e = ExpertWeights(w, w_block_scale if blocks else w_scale)
+    w, scale = e
     T, k = r.topk_ids.shape
     P, N = T * k, w.shape[1]
-    fmt = _moe_weight_format(w, w_scale, w_block_scale)
-    if tiles is None:
-        tiles = moe_uses_tiles(T, k, w.shape[0], fmt, x.device)
-    elif tiles and _gpu(x) and fmt != "bf16" and not policy().moe_tile_rows_q:
-        raise ValueError(f"moe_grouped_gemm: tiles=True needs bf16 expert weights, got {fmt} "
-                         "(quantised experts run on the weight-streaming kernel unless "
-                         "KernelPolicy.moe_tile_rows_q is set)")
-    if w_block_scale is not None or w.dtype == torch.uint8:
-        if w_scale is not None:
-            raise ValueError("moe_grouped_gemm: w_scale (fp8) or w_block_scale (MXFP4), not both")
-        if w_block_scale is None:
+    if blocks or w.dtype == torch.uint8:
+        if scale is None:
             raise ValueError("moe_grouped_gemm: uint8 (MXFP4) weights need w_block_scale "
                              "[E, N, K / 32]")
         if w.dtype != torch.uint8 or w.dim() != 3:
             raise ValueError("moe_grouped_gemm: w_block_scale goes with uint8 MXFP4 weights "
                              "[E, N, K / 2]")
-        if (w_block_scale.dtype != torch.uint8 or w_block_scale.device != w.device
-                or tuple(w_block_scale.shape) != (w.shape[0], N, w.shape[2] // 16)
-                or w.shape[2] % 16):
+        if (scale.dtype != torch.uint8 or scale.device != w.device
+                or tuple(scale.shape) != (w.shape[0], N, w.shape[2] // 16) or w.shape[2] % 16):
             raise ValueError("moe_grouped_gemm: w_block_scale uint8 [E, N, K / 32] on the "
                              "weights' device")
         if w.shape[2] % 64:
@@ -1553,36 +1551,29 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, down: bool
     if out is None:
         out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=x.device)
     if not _gpu(x):
-        ok = (w_block_scale is not None or
-              (w.dtype == torch.bfloat16 if w_scale is None else
-               w.dtype == FP8 and tuple(w_scale.shape) == (w.shape[0], N)))
+        ok = (w.dtype == torch.uint8 or
+              (w.dtype == torch.bfloat16 if scale is None else
+               w.dtype == FP8 and tuple(scale.shape) == (w.shape[0], N)))
         if not ok:
             raise ValueError("moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with "
                              "w_scale [E, N]")
-        return ref.moe_grouped_gemm(x, w, r, 1 if down else 0, out, w_scale, w_block_scale)
+        return ref.moe_grouped_gemm(x, e, r, 1 if down else 0, out)
+    fmt = e.format
+    if tiles is None:
+        tiles = moe_uses_tiles(T, k, e.E, fmt, x.device)
+    elif tiles and fmt != "bf16" and not policy().moe_tile_rows_q:
+        raise ValueError(f"moe_grouped_gemm: tiles=True needs bf16 expert weights, got {fmt} "
+                         "(quantised experts run on the weight-streaming kernel unless "
+                         "KernelPolicy.moe_tile_rows_q is set)")
+    if fmt == "mxfp4":
+        scale = scale.contiguous()
     if tiles:
-        if w_block_scale is not None:
-            native().moe_tile_gemm_fp4(out, x.contiguous(), w, w_block_scale.contiguous(),
-                                       r.sorted_pairs, r.expert_count, r.expert_offset, T, k,
-                                       1 if down else 0)
-        elif w_scale is not None:
-            native().moe_tile_gemm_fp8(out, x.contiguous(), w, w_scale, r.sorted_pairs,
-                                       r.expert_count, r.expert_offset, T, k, 1 if down else 0)
-        else:
-            native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
-                                   r.expert_offset, T, k, 1 if down else 0)
-        return out
-    if w_block_scale is not None:
-        native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
-                                  r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0,
-                                  None, w_block_scale.contiguous())
-    elif w_scale is None:
-        native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
-                                  r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0)
+        native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
+                               r.expert_offset, T, k, 1 if down else 0, scale)
     else:
         native().moe_grouped_gemm(out, x.contiguous(), w, r.sorted_pairs, r.tile_expert,
                                   r.tile_start, r.tile_rows, r.n_tiles, T, k, 1 if down else 0,
-                                  w_scale)
+                                  scale)
     return out
 
 
@@ -1611,19 +1602,14 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
-def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
-            w_down: torch.Tensor, k: int, renorm: bool,
-            w_gate_up_scale: Optional[torch.Tensor] = None,
-            w_down_scale: Optional[torch.Tensor] = None,
-            w_gate_up_block_scale: Optional[torch.Tensor] = None,
-            w_down_block_scale: Optional[torch.Tensor] = None,
+def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, gate_up, down, k: int, renorm: bool,
             num_experts: Optional[int] = None,
             shared: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
-    SwiGLU and down on the grouped GEMM, weighted combine.  ``w_gate_up [E, 2I, H]`` (each
-    expert's rows in :func:`swiglu_interleave` order), ``w_down [E, H, I]``: bf16, or fp8 e4m3fn
-    with their row scales ``[E, 2I]`` / ``[E, H]``, or MXFP4 nibbles ``[E, 2I, H / 2]`` /
-    ``[E, H, I / 2]`` with their block scales ``[E, 2I, H / 32]`` / ``[E, H, I / 32]``.
+    SwiGLU and down on the grouped GEMM, weighted combine.  ``gate_up [E, 2I, H]`` (each
+    expert's rows in :func:`swiglu_interleave` order) and ``down [E, H, I]`` are
+    :class:`ExpertWeights` (bf16, fp8 with row scales or MXFP4 with block scales), or bare bf16
+    tensors.
     Experts with many rows each run both products on the tile GEMM when their format's policy
     field is set (:func:`moe_uses_tiles`: ``moe_tile_rows`` for bf16, ``moe_tile_rows_q`` for fp8
     and MXFP4).
@@ -1634,8 +1620,6 @@ def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, w_gate_up: torch.Tensor,
     if (num_experts is None) != (shared is None):
         raise ValueError("moe_mlp: num_experts and shared go together")
     r = moe_route(gate_logits, k, renorm, num_experts)
-    h = moe_grouped_gemm(x, w_gate_up, r, w_scale=w_gate_up_scale,
-                         w_block_scale=w_gate_up_block_scale)
-    y = moe_grouped_gemm(h, w_down, r, down=True, w_scale=w_down_scale,
-                         w_block_scale=w_down_block_scale)
+    h = moe_grouped_gemm(x, gate_up, r)
+    y = moe_grouped_gemm(h, down, r, down=True)
     return moe_combine(y, r.topk_w, shared=shared, shared_w=r.shared_w)

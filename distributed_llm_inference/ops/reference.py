@@ -460,6 +460,65 @@ class MoERouting(NamedTuple):
     shared_w: Optional[torch.Tensor] = None
 
 
+class ExpertWeights(NamedTuple):
+    """The routed experts' stacked weights with the scale their format needs; the format follows
+    from ``w``'s dtype:
+
+    * ``"bf16"``: ``w [E, N, K]`` bf16, no scale;
+    * ``"fp8"``: ``w [E, N, K]`` e4m3fn, ``scale [E, N]`` fp32, one per weight row;
+    * ``"mxfp4"``: ``w [E, N, K / 2]`` uint8 nibbles (element 2j in the low nibble of byte j),
+      ``scale [E, N, K / 32]`` uint8 e8m0, one per 32 input features."""
+
+    w: torch.Tensor
+    scale: Optional[torch.Tensor] = None
+
+    @property
+    def format(self) -> str:
+        fmt = {torch.bfloat16: "bf16", torch.float8_e4m3fn: "fp8",
+               torch.uint8: "mxfp4"}.get(self.w.dtype)
+        if fmt is None:
+            raise ValueError(f"expert weights are bf16, fp8 e4m3fn or uint8 MXFP4 nibbles, got "
+                             f"{self.w.dtype}")
+        return fmt
+
+    @property
+    def E(self) -> int:
+        return self.w.shape[0]
+
+    @property
+    def N(self) -> int:
+        return self.w.shape[1]
+
+    @property
+    def K(self) -> int:
+        """The logical reduction length (two per stored byte of MXFP4 nibbles)."""
+        return self.w.shape[2] * (2 if self.format == "mxfp4" else 1)
+
+    def dequantize(self, e: int) -> torch.Tensor:
+        """Expert e's weight as bf16: the tensor itself, the MXFP4 rows widened (exact), or the
+        fp8 rows times their scales in fp32, rounded once."""
+        fmt, w = self.format, self.w[e]
+        if fmt == "mxfp4":
+            from . import dequantize_mxfp4   # the GPU kernel for GPU tensors
+            return dequantize_mxfp4(w, self.scale[e])
+        if fmt == "bf16":
+            return w
+        return (w.float() * self.scale[e][:, None]).to(torch.bfloat16)
+
+    @classmethod
+    def quantize(cls, w: torch.Tensor, fmt: str) -> "ExpertWeights":
+        """bf16 ``w [E, N, K]`` in format ``fmt`` (``ops.quantize_expert_weights_fp8`` /
+        ``_mxfp4``: one expert at a time); ``"bf16"`` wraps ``w`` as it is."""
+        from . import quantize_expert_weights_fp8, quantize_expert_weights_mxfp4
+        if fmt == "bf16":
+            return cls(w)
+        if fmt == "fp8":
+            return cls(*quantize_expert_weights_fp8(w))
+        if fmt == "mxfp4":
+            return cls(*quantize_expert_weights_mxfp4(w))
+        raise ValueError(f"ExpertWeights.quantize: format bf16, fp8 or mxfp4, got {fmt!r}")
+
+
 def moe_tile_capacity(T: int, E: int, k: int, tile_rows: int = MOE_TILE_ROWS) -> int:
     """Tiles of <= ``tile_rows`` rows that P = T k pairs over E experts can need, at most."""
     P = T * k
@@ -527,28 +586,25 @@ def _swiglu_interleaved(gu: torch.Tensor) -> torch.Tensor:
     return (F.silu(v[..., 0, :]) * v[..., 1, :]).reshape(M, n2 // 2).to(torch.bfloat16)
 
 
-def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, r: MoERouting, epilogue: int,
-                     out: torch.Tensor, w_scale: Optional[torch.Tensor] = None,
-                     w_block_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+def moe_grouped_gemm(x: torch.Tensor, w: ExpertWeights, r: MoERouting, epilogue: int,
+                     out: torch.Tensor) -> torch.Tensor:
     """``epilogue`` 0: ``out[j] = swiglu(x[sorted_pairs[j] // k] . w[e]^T)`` for the rows j of
     expert e (``w [E, 2I, H]``, rows in ``ops.swiglu_interleave`` order); 1:
     ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding.
-    ``w_scale [E, N]``: ``w`` is fp8 and row n of expert e is ``w[e, n] * w_scale[e, n]``.
-    ``w_block_scale [E, N, K / 32]``: ``w`` is MXFP4 nibbles ``[E, N, K / 2]`` and expert e is
-    ``dequantize_mxfp4(w[e], w_block_scale[e])``."""
+    Expert e is ``w.dequantize(e)``, except that fp8 rows times their scales stay fp32 (no
+    rounding to bf16 in between)."""
     k = r.topk_ids.shape[1]
     off = r.expert_offset.tolist()
     pairs = r.sorted_pairs.long()
-    for e in range(w.shape[0]):
+    fp8 = w.format == "fp8"
+    for e in range(w.E):
         a, b = off[e], off[e + 1]
         if a == b:
             continue
-        if w_block_scale is not None:
-            wf = dequantize_mxfp4(w[e], w_block_scale[e]).float()
+        if fp8:
+            wf = w.w[e].float() * w.scale[e].float()[:, None]
         else:
-            wf = w[e].float()
-        if w_scale is not None:
-            wf = wf * w_scale[e].float()[:, None]
+            wf = w.dequantize(e).float()
         wf = wf.t()
         if epilogue == 0:
             out[a:b] = _swiglu_interleaved(x[pairs[a:b] // k].float() @ wf)

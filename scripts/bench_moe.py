@@ -148,9 +148,9 @@ def bench_model(torch, ops, F, name, rows, res, a):
         if quant:
             cands = {"moe": moe, "gate_up": parts["gate_up"], "down": parts["down"]}
         for fmt, (qgu, qd, sgu, sd, kw) in quant.items():
-            def moe_q(c, qgu=qgu, qd=qd, sgu=sgu, sd=sd, kw=kw):
-                return ops.moe_mlp(x, logits[c], qgu[c], qd[c], k, spec.norm_topk_prob,
-                                   **{"w_gate_up_" + kw[2:]: sgu[c], "w_down_" + kw[2:]: sd[c]})
+            def moe_q(c, qgu=qgu, qd=qd, sgu=sgu, sd=sd):
+                return ops.moe_mlp(x, logits[c], ops.ExpertWeights(qgu[c], sgu[c]),
+                                   ops.ExpertWeights(qd[c], sd[c]), k, spec.norm_topk_prob)
 
             hq = [ops.moe_grouped_gemm(x, qgu[c], routes[c], **{kw: sgu[c]}) for c in range(copies)]
             yq = [torch.empty_like(ys[c]) for c in range(copies)]

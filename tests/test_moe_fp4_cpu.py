@@ -87,8 +87,7 @@ def test_reference_moe_mlp_with_block_scales_is_the_dense_definition():
     w_gate_up = torch.stack([ops.swiglu_interleave(torch.cat([wg[e], wu[e]], 0)) for e in range(E)])
     gu4, sgu = ops.quantize_expert_weights_mxfp4(w_gate_up)
     d4, sd = ops.quantize_expert_weights_mxfp4(wd)
-    got = ops.moe_mlp(x, logits, gu4, d4, k, True, w_gate_up_block_scale=sgu,
-                      w_down_block_scale=sd)
+    got = ops.moe_mlp(x, logits, ops.ExpertWeights(gu4, sgu), ops.ExpertWeights(d4, sd), k, True)
     dgu = torch.stack([ops.swiglu_deinterleave(d) for d in _dequant(gu4, sgu)]).float()
     dg, du, dd = dgu[:, :I], dgu[:, I:], _dequant(d4, sd).float()
     ids, w = ref.moe_topk(logits, k, True)

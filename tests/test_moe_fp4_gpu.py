@@ -242,21 +242,21 @@ def test_fp4_grouped_gemm_deterministic_and_host_checks(gpu):
     nat = ops.native().moe_grouped_gemm
     out = torch.empty(200, 128, dtype=BF, device=gpu)
     tabs = (r.sorted_pairs, r.tile_expert, r.tile_start, r.tile_rows, r.n_tiles, 100, 2, 0)
-    nat(out, x, w4, *tabs, None, s)
+    nat(out, x, w4, *tabs, s)
     torch.cuda.synchronize()
     assert torch.equal(_bits(out), _bits(a))
-    with pytest.raises(RuntimeError, match="not both"):
-        nat(out, x, w4, *tabs, torch.ones(E, 256, device=gpu), s)
+    with pytest.raises(RuntimeError, match="w_block_scale"):         # an fp8 row scale instead
+        nat(out, x, w4, *tabs, torch.ones(E, 256, device=gpu))
     with pytest.raises(RuntimeError, match="w_block_scale"):
         nat(out, x, w4, *tabs)
     with pytest.raises(RuntimeError, match="w_block_scale"):
-        nat(out, x, wb, *tabs, None, s)
+        nat(out, x, wb, *tabs, s)
     with pytest.raises(RuntimeError, match="w_block_scale"):
-        nat(out, x, w4, *tabs, None, s[:, :, :-1].contiguous())
+        nat(out, x, w4, *tabs, s[:, :, :-1].contiguous())
     with pytest.raises(RuntimeError):
-        nat(out, x, w4, *tabs, None, s.cpu())
+        nat(out, x, w4, *tabs, s.cpu())
     with pytest.raises(RuntimeError, match="K % 128"):
-        nat(out, x[:, :192].contiguous(), w4[:, :, :96].contiguous(), *tabs, None,
+        nat(out, x[:, :192].contiguous(), w4[:, :, :96].contiguous(), *tabs,
             s[:, :, :6].contiguous())
 
 

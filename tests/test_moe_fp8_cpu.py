@@ -79,7 +79,7 @@ def test_reference_moe_mlp_with_scales_is_the_dense_definition():
     w_gate_up = torch.stack([ops.swiglu_interleave(torch.cat([wg[e], wu[e]], 0)) for e in range(E)])
     gu8, sgu = ops.quantize_expert_weights_fp8(w_gate_up)
     d8, sd = ops.quantize_expert_weights_fp8(wd)
-    got = ops.moe_mlp(x, logits, gu8, d8, k, True, w_gate_up_scale=sgu, w_down_scale=sd)
+    got = ops.moe_mlp(x, logits, ops.ExpertWeights(gu8, sgu), ops.ExpertWeights(d8, sd), k, True)
     dgu = torch.stack([ops.swiglu_deinterleave(_dequant(gu8[e], sgu[e])) for e in range(E)])
     dg, du, dd = dgu[:, :I], dgu[:, I:], _dequant(d8, sd)
     ids, w = ref.moe_topk(logits, k, True)

@@ -69,17 +69,16 @@ def test_cpu_path_ignores_the_policy(fmt):
     T, E, k, x, logits, wgu, wd = _quantised_inputs()
     if fmt == "fp8":
         (qgu, sgu), (qd, sd) = ops.quantize_expert_weights_fp8(wgu), ops.quantize_expert_weights_fp8(wd)
-        kw = dict(w_gate_up_scale=sgu, w_down_scale=sd)
         one = dict(w_scale=sgu)
     else:
         (qgu, sgu), (qd, sd) = (ops.quantize_expert_weights_mxfp4(wgu),
                                 ops.quantize_expert_weights_mxfp4(wd))
-        kw = dict(w_gate_up_block_scale=sgu, w_down_block_scale=sd)
         one = dict(w_block_scale=sgu)
-    base = ops.moe_mlp(x, logits, qgu, qd, k, True, **kw)
+    gate_up, down = ops.ExpertWeights(qgu, sgu), ops.ExpertWeights(qd, sd)
+    base = ops.moe_mlp(x, logits, gate_up, down, k, True)
     with ops.kernel_policy(moe_tile_rows_q=64):
         assert T * k >= 64 * E and not ops.moe_uses_tiles(T, k, E, fmt, x.device)
-        got = ops.moe_mlp(x, logits, qgu, qd, k, True, **kw)
+        got = ops.moe_mlp(x, logits, gate_up, down, k, True)
         r = ops.moe_route(logits, k, True)
         forced = ops.moe_grouped_gemm(x, qgu, r, tiles=True, **one)   # the CPU path ignores `tiles`
     assert torch.equal(got.view(torch.int16), base.view(torch.int16))

@@ -303,41 +303,41 @@ def test_quantised_tiles_deterministic_and_host_checks(gpu):
                                      tiles=True, **{kw: s})
     # the native entries themselves
     out = torch.empty(T * K, 128, dtype=BF, device=gpu)
-    nat.moe_tile_gemm_fp8(out, x, w8, s8, *tabs, T, K, 0)
-    nat.moe_tile_gemm_fp4(out, x, w4, s4, *tabs, T, K, 0)
+    nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0, s8)
+    nat.moe_tile_gemm(out, x, w4, *tabs, T, K, 0, s4)
     with pytest.raises(RuntimeError, match="w_scale"):                       # shape
-        nat.moe_tile_gemm_fp8(out, x, w8, s8[:, :-1].contiguous(), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0, s8[:, :-1].contiguous())
     with pytest.raises(RuntimeError, match="w_scale"):
-        nat.moe_tile_gemm_fp8(out, x, w8, s8.reshape(-1), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0, s8.reshape(-1))
     with pytest.raises(RuntimeError, match="w_scale"):                       # dtype
-        nat.moe_tile_gemm_fp8(out, x, w8, s8.to(BF), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0, s8.to(BF))
     with pytest.raises(RuntimeError, match="fp8 e4m3fn"):
-        nat.moe_tile_gemm_fp8(out, x, w8.view(U8), s8, *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8.view(U8), *tabs, T, K, 0, s8)
     with pytest.raises(RuntimeError, match="w_block_scale"):                 # shape
-        nat.moe_tile_gemm_fp4(out, x, w4, s4[:, :, :-1].contiguous(), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w4, *tabs, T, K, 0, s4[:, :, :-1].contiguous())
     with pytest.raises(RuntimeError, match="w_block_scale"):                 # dtype
-        nat.moe_tile_gemm_fp4(out, x, w4, s4.to(torch.int8), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w4, *tabs, T, K, 0, s4.to(torch.int8))
     with pytest.raises(RuntimeError, match="K % 64"):
-        nat.moe_tile_gemm_fp8(out, x[:, :96].contiguous(), w8[:, :, :96].contiguous(), s8, *tabs,
-                              T, K, 0)
+        nat.moe_tile_gemm(out, x[:, :96].contiguous(), w8[:, :, :96].contiguous(), *tabs, T, K, 0,
+                          s8)
     with pytest.raises(RuntimeError, match="K % 128"):                       # 192: two blocks short
-        nat.moe_tile_gemm_fp4(out, x[:, :192].contiguous(), w4[:, :, :96].contiguous(),
-                              s4[:, :, :6].contiguous(), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x[:, :192].contiguous(), w4[:, :, :96].contiguous(), *tabs, T, K, 0,
+                          s4[:, :, :6].contiguous())
     with pytest.raises(RuntimeError, match="N % 128"):
-        nat.moe_tile_gemm_fp8(out, x, w8[:, :192].contiguous(), s8[:, :192].contiguous(), *tabs,
-                              T, K, 0)
+        nat.moe_tile_gemm(out, x, w8[:, :192].contiguous(), *tabs, T, K, 0,
+                          s8[:, :192].contiguous())
     with pytest.raises(RuntimeError, match="out"):                           # too few rows
-        nat.moe_tile_gemm_fp8(out[:799], x, w8, s8, *tabs, T, K, 0)
+        nat.moe_tile_gemm(out[:799], x, w8, *tabs, T, K, 0, s8)
     with pytest.raises(RuntimeError, match="out"):
-        nat.moe_tile_gemm_fp4(out[:799], x, w4, s4, *tabs, T, K, 0)
+        nat.moe_tile_gemm(out[:799], x, w4, *tabs, T, K, 0, s4)
     with pytest.raises(RuntimeError):                                        # another device
-        nat.moe_tile_gemm_fp8(out, x, w8.cpu(), s8, *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8.cpu(), *tabs, T, K, 0, s8)
     with pytest.raises(RuntimeError):
-        nat.moe_tile_gemm_fp4(out, x, w4.cpu(), s4, *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w4.cpu(), *tabs, T, K, 0, s4)
     with pytest.raises(RuntimeError):
-        nat.moe_tile_gemm_fp8(out, x, w8, s8.cpu(), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0, s8.cpu())
     with pytest.raises(RuntimeError):
-        nat.moe_tile_gemm_fp4(out, x, w4, s4.cpu(), *tabs, T, K, 0)
+        nat.moe_tile_gemm(out, x, w4, *tabs, T, K, 0, s4.cpu())
     # the policy at 0: as before
     assert ops.policy().moe_tile_rows_q == 0
     with pytest.raises(ValueError, match="tiles=True needs bf16 expert weights"):
@@ -345,6 +345,41 @@ def test_quantised_tiles_deterministic_and_host_checks(gpu):
     with pytest.raises(RuntimeError, match="bf16 expert weights only"):
         nat.moe_tile_gemm(out, x, w8, *tabs, T, K, 0)
     torch.cuda.synchronize()
+
+
+def test_tile_entry_rejects_a_scale_of_another_format_before_any_launch(gpu):
+    """The one native entry infers the format from the weights' dtype: a scale that does not go
+    with it is refused with the output untouched, and valid calls after that give the front
+    end's bits."""
+    T, k, E_, N, K_ = 4, 2, 2, 128, 128
+    g = torch.Generator().manual_seed(11)
+    h = torch.randn(T * k, K_, generator=g).to(BF).to(gpu)
+    wb = (torch.randn(E_, N, K_, generator=g) / K_ ** 0.5).to(BF)
+    ew = {fmt: ops.ExpertWeights(*(t if t is None else t.to(gpu)
+                                   for t in ops.ExpertWeights.quantize(wb, fmt)))
+          for fmt in ["bf16"] + FMTS}
+    ids = torch.tensor([[0, 1], [1, 0], [0, 1], [1, 0]], dtype=torch.int32)
+    r = ops.moe_group(ids.to(gpu), torch.full((T, k), 0.5).to(gpu), E_)
+    nat = ops.native().moe_tile_gemm
+    tabs = (r.sorted_pairs, r.expert_count, r.expert_offset, T, k, 1)
+    (w8, s8), (w4, s4) = ew["fp8"], ew["mxfp4"]
+    out = torch.full((T * k, N), SENT, dtype=BF, device=gpu)
+    for w, s in ((ew["bf16"].w, s8),                          # bf16 weights with a scale
+                 (w8, None),                                  # fp8 weights without one
+                 (w8, s8.to(U8)),                             # ... with a uint8 scale
+                 (w4, s4.float()),                            # nibbles with an fp32 scale
+                 (w4, s4[:, :, :-1].contiguous()),            # [E, N, K / 32 - 1]
+                 (w8, s8.cpu()), (w4, s4.cpu())):             # a scale on the CPU
+        with pytest.raises(RuntimeError):
+            nat(out, h, w, *tabs, s)
+    torch.cuda.synchronize()
+    assert bool((out == SENT).all())
+    with ops.kernel_policy(moe_tile_rows_q=64):
+        for fmt, (w, s) in ew.items():
+            nat(out, h, w, *tabs, s)
+            want = ops.moe_grouped_gemm(h, ew[fmt], r, down=True, tiles=True)
+            assert torch.equal(_bits(out), _bits(want)), fmt
+            assert float(want.float().abs().max()) > 0.01
 
 
 # ------------------------------------------------------------------------------------- the block
@@ -421,16 +456,17 @@ def _on_gpu(mlp, fmt, gpu):
 
 
 def _spy(monkeypatch):
-    """Counts the native tile launches per entry (their epilogues), and lets them through."""
+    """Counts the native tile launches per weight format (their epilogues), and lets them
+    through."""
     nat = ops.native()
     calls = {"bf16": [], "fp8": [], "mxfp4": []}
-    for fmt, name, epi in (("bf16", "moe_tile_gemm", 8), ("fp8", "moe_tile_gemm_fp8", 9),
-                           ("mxfp4", "moe_tile_gemm_fp4", 9)):
-        def spy(*a, real=getattr(nat, name), log=calls[fmt], epi=epi):
-            log.append(int(a[epi]))
-            return real(*a)
+    fmt_of = {BF: "bf16", FP8: "fp8", U8: "mxfp4"}
 
-        monkeypatch.setattr(nat, name, spy)
+    def spy(*a, real=nat.moe_tile_gemm):
+        calls[fmt_of[a[2].dtype]].append(int(a[8]))
+        return real(*a)
+
+    monkeypatch.setattr(nat, "moe_tile_gemm", spy)
     return calls
 
 
