@@ -14,6 +14,16 @@
 //   * v_dot2c_f32_bf16 (two bf16 products into an fp32 accumulator per instruction, no bf16->f32
 //     conversions): plain conversions + FMAs made M = 4 VALU-bound; one wave reduction per
 //     (m, row) at the end, lane 0 stores.
+//
+// Accuracy contract (derived in tests/gemm_oracle.py's docstring, held per element by
+// tests/test_gemm_exact_gpu.py):  |y - o| <= 2^-8 (1 + 2^-6) |o| + c 2^-24 S  against the fp64
+// product o, with S = sum_k |x_k| |w_k| (scales and |bias| included) and c the longest chain of
+// dependent fp32 roundings of an output: one dot2 (counted as 2) per element pair of the lane's
+// vector per k-step, the 6-level wave reduction, <= 2 scale multiplies and the bias --
+//   bf16   c =  8 ceil(K /  512) + 9        fp8   c = 16 ceil(K / 1024) + 9
+//   MXFP4  c = 32 ceil(K / 2048) + 9        int8  c = 2 (16 ceil(K / 1024) + 10), and the WEAKER
+//   S = ws sum_k |x_k| (|q_k| + 128): the int8 kernel accumulates x (q + 128) and 128 sum x
+//   separately (see skinny_gemm_fp8_kernel), so its error scales with |x| even where q = 0.
 #include "kernels.h"
 #include "gemv_core.h"
 
@@ -231,6 +241,9 @@ __global__ void __launch_bounds__(256) skinny_gemm_kernel(const bf16* __restrict
 // packed into one bf16 pair by v_perm_b32 -- 2.25 VALU per weight byte instead of a per-byte
 // sign-extend / convert / round chain.  The bias is removed once from the reduced sum:
 // sum x * w = sum x * (w + 128) - 128 * sum x, with sum x accumulated by one extra dot per pair.
+// Both sums are fp32 and are subtracted once per lane, so the rounding error is bounded by
+// sum |x| (|w| + 128), not sum |x| |w| (the header's int8 contract): about 2^-24 * 128 sum |x| * c
+// even for an all-zero weight row when x has a mean.
 template <int M, bool XF8, bool WI8 = false, int EP = kEpPlain, bool NORM = false>
 __global__ void __launch_bounds__(256) skinny_gemm_fp8_kernel(const void* __restrict__ x_in,
                                                               const float* __restrict__ xscale,

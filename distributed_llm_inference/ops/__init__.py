@@ -1198,7 +1198,9 @@ def swiglu_interleaved(gu: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
     (shapes the fused tile epilogue does not take: prefill chunks, 1-2 row batches)."""
     M, n2 = gu.shape
     if not _gpu(gu):
-        v = gu.float().reshape(M, n2 // 256, 4, 2, 2, 16)
+        # 16 gate columns, then their 16 up columns, in every group of 32 (n2 % 32 == 0: the
+        # GEMV epilogues take such widths too, not only whole 256-column tiles)
+        v = gu.float().reshape(M, n2 // 32, 2, 16)
         y = (torch.nn.functional.silu(v[..., 0, :]) * v[..., 1, :]).reshape(M, n2 // 2).to(gu.dtype)
         return out.copy_(y) if out is not None else y
     if out is None:
