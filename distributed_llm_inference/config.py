@@ -720,6 +720,13 @@ class KernelPolicy:
     # kernel on both, in both formats (docs/kernels.md "Sparse MoE: tile GEMM, quantised
     # experts": 3.6-4.9x at 2048-8192 rows for fp8, 3.1-4.0x for MXFP4)
     moe_tile_rows_q: int = 0
+    # sparse MoE, MXFP4 experts: where moe_tile_rows_q sends them to the tiles, run both products
+    # on the block-scaled fp4 x fp8 MFMA (csrc/kernels/moe_tile_mx.hip; x and h quantised to MX
+    # fp8 with row-major scales first) instead of widening the weight to bf16.  Experimental and
+    # off: it changes the numerics of those products (fp8 activation rounding; docs/kernels.md
+    # "Sparse MoE: block-scaled tile GEMM").  bf16 and fp8 experts ignore it, and so does every
+    # call that moe_tile_rows_q leaves on the weight-streaming kernel
+    moe_tile_mx: bool = False
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 

@@ -1283,6 +1283,41 @@ void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor e
                                      cur_stream()), "moe_tile_gemm");
 }
 
+// MXFP4 experts x MX fp8 activations on the block-scaled MFMA (moe_tile_mx.hip): a_q e4m3 bytes
+// [R, K] with row-major e8m0 scales a_sc [R, K / 128] (quant_mx_rows); R = T for gate|up (gathered
+// by token), R >= T k for down.  Everything is checked before the launch
+void moe_tile_gemm_mx(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sorted_pairs,
+                      Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
+                      int64_t epilogue, optional<Tensor> scale) {
+  CHECK_IN(out); CHECK_IN(a_q); CHECK_IN(a_sc);
+  CHECK_BF16(out);
+  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
+  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
+  const ExpertArgs e = check_expert_weights("moe_tile_gemm_mx", w, scale, a_q.device());
+  TORCH_CHECK(e.w.format == dli::kExpertFp4, "moe_tile_gemm_mx: MXFP4 expert weights only (uint8 "
+              "nibbles with w_block_scale); bf16 and fp8 experts run on moe_tile_gemm");
+  TORCH_CHECK(out.dim() == 2 && a_q.dim() == 2 && a_q.element_size() == 1,
+              "moe_tile_gemm_mx: out 2-D, a_q = e4m3 bytes [R, K]");
+  TORCH_CHECK(e.K % 128 == 0, "moe_tile_gemm_mx: needs K % 128 == 0");
+  TORCH_CHECK(e.K <= dli::moe_tile_mx_max_k(), "moe_tile_gemm_mx: K = ", e.K, " exceeds the ",
+              dli::moe_tile_mx_max_k(), " whose activation scales the kernel's LDS slot holds");
+  check_moe_tile("moe_tile_gemm_mx", out, a_q, w, sorted_pairs, expert_count, expert_offset, T, k,
+                 epilogue, e.K);
+  TORCH_CHECK(epilogue == 1 || a_q.size(0) == T,
+              "moe_tile_gemm_mx: gate|up takes x quantised once per token, a_q [T, K]");
+  TORCH_CHECK(a_sc.scalar_type() == at::kByte && a_sc.dim() == 2 &&
+                  a_sc.size(0) == a_q.size(0) && a_sc.size(1) == e.K / 128 &&
+                  a_sc.device() == a_q.device(),
+              "moe_tile_gemm_mx: a_sc = uint8 e8m0 [R, K / 128], row-major, on a_q's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(a_q.device());
+  check_rc(dli::launch_moe_tile_gemm_mx(bp(out), static_cast<const uint8_t*>(a_q.data_ptr()),
+                                        a_sc.data_ptr<uint8_t>(), e.w,
+                                        sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
+                                        expert_offset.data_ptr<int>(), (int)T, (int)e.E, (int)k,
+                                        (int)e.N, (int)e.K, (int)epilogue, cur_stream()),
+           "moe_tile_gemm_mx");
+}
+
 // shared [T, H] (bf16) with shared_w [T] (fp32): the shared expert's term, added after the slots
 void moe_combine(Tensor out, Tensor y, Tensor w, optional<Tensor> shared,
                  optional<Tensor> shared_w) {
@@ -1348,6 +1383,25 @@ void quant_mx(Tensor q, Tensor sc, Tensor x) {
                                 static_cast<uint8_t*>(sc.data_ptr()), bp(x), (int)M, (int)K,
                                 cur_stream()),
            "quant_mx");
+}
+
+// the same quantiser with row-major scales sc [M, K / 128] (for moe_tile_gemm_mx's gathered rows)
+void quant_mx_rows(Tensor q, Tensor sc, Tensor x) {
+  CHECK_IN(q); CHECK_IN(sc); CHECK_IN(x); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2, "quant_mx_rows: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M <= (1 << 24) && K >= 128 && K % 128 == 0 && K <= (1 << 24),
+              "quant_mx_rows: x [M, K] with M >= 1 and K % 128 == 0");
+  TORCH_CHECK(q.element_size() == 1 && q.size(0) == M && q.size(1) == K,
+              "quant_mx_rows: q = 1-byte [M, K]");
+  TORCH_CHECK(sc.element_size() == 1 && sc.numel() == M * (K / 128),
+              "quant_mx_rows: sc = [M, K / 128] bytes");
+  TORCH_CHECK(q.device() == x.device() && sc.device() == x.device(), "quant_mx_rows: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  check_rc(dli::launch_quant_mx_rows(static_cast<uint8_t*>(q.data_ptr()),
+                                     static_cast<uint8_t*>(sc.data_ptr()), bp(x), (int)M, (int)K,
+                                     cur_stream()),
+           "quant_mx_rows");
 }
 
 // MXFP4 weights x MX fp8 activations on the mixed-format block-scaled MFMA (gemm_fp4.hip).
@@ -1587,6 +1641,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"), py::arg("scale") = py::none());
+  m.def("moe_tile_gemm_mx", &moe_tile_gemm_mx,
+        "grouped block-scaled MFMA tile GEMM: MXFP4 experts x MX fp8 activations with row-major "
+        "scales (0: gate|up + SwiGLU, 1: down)",
+        py::arg("out"), py::arg("a_q"), py::arg("a_sc"), py::arg("w"), py::arg("sorted_pairs"),
+        py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
+        py::arg("epilogue"), py::arg("scale") = py::none());
+  m.def("moe_tile_mx_max_k", []() { return dli::moe_tile_mx_max_k(); },
+        "largest K of moe_tile_gemm_mx");
+  m.def("quant_mx_rows", &quant_mx_rows,
+        "MX fp8 quantiser with row-major scales: bf16 [M, K] -> e4m3 bytes + e8m0 [M, K / 128]",
+        py::arg("q"), py::arg("sc"), py::arg("x"));
   m.def("moe_combine", &moe_combine, "out[t] = bf16(sum_slot w[t, slot] * y[t k + slot])",
         py::arg("out"), py::arg("y"), py::arg("w"), py::arg("shared") = py::none(),
         py::arg("shared_w") = py::none());

@@ -320,4 +320,43 @@ int launch_quant_mx(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K, hip
   return 0;
 }
 
+// The same quantiser with ROW-MAJOR scales sc [rows, K / 128], for consumers that gather rows
+// (moe_tile_mx.hip): the same 16 lanes per block and the same arithmetic, so bytes and exponents
+// are quant_mx_kernel's bit for bit; the scale of block blk is byte blk, and there is no padding.
+__global__ void __launch_bounds__(256) quant_mx_rows_kernel(uint8_t* __restrict__ q,
+                                                            uint8_t* __restrict__ sc,
+                                                            const bf16* __restrict__ x,
+                                                            size_t nblocks) {
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t blk = gid >> 4;
+  if (blk >= nblocks) return;   // whole 16-lane groups leave together
+  const int sub = (int)(gid & 15);
+  const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + blk * 128 + sub * 8);
+  float f[8], a = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f[j] = (float)v[j];
+    a = fmaxf(a, fabsf(f[j]));
+  }
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+  const int k = mx_exponent(a);
+  const float inv = mx_inv_scale(k);
+  uint2 o;
+  o.x = pack4_fp8(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
+  o.y = pack4_fp8(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
+  *reinterpret_cast<uint2*>(q + blk * 128 + sub * 8) = o;
+  if (sub == 0) sc[blk] = (uint8_t)(k + 127);
+}
+
+int launch_quant_mx_rows(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K,
+                         hipStream_t stream) {
+  if (rows < 1 || K < 128 || K % 128 != 0) return -1;
+  if (q == nullptr || sc == nullptr || x == nullptr) return -5;
+  const size_t nblocks = (size_t)rows * (K / 128), threads = nblocks * 16;
+  if ((threads + 255) / 256 > 0x7fffffffULL) return -1;
+  quant_mx_rows_kernel<<<(int)((threads + 255) / 256), 256, 0, stream>>>(q, sc, x, nblocks);
+  return 0;
+}
+
 }  // namespace dli

@@ -1079,6 +1079,40 @@ def quant_mx(h: torch.Tensor) -> MxFp8:
     return MxFp8(q, sc)
 
 
+class MxFp8Rows:
+    """:class:`MxFp8` values with the scales row-major: ``q [M, K]`` e4m3 and ``sc [M, K / 128]``
+    uint8 e8m0, so a consumer that gathers rows (moe_tile_mx.hip) takes a row's scales with it."""
+
+    __slots__ = ("q", "sc")
+
+    def __init__(self, q: torch.Tensor, sc: torch.Tensor):
+        self.q, self.sc = q, sc
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    def dequantize(self) -> torch.Tensor:
+        e = self.sc.to(torch.int32).float() - 127.0
+        return self.q.float() * torch.exp2(e).repeat_interleave(128, dim=1)
+
+
+def quant_mx_rows(h: torch.Tensor) -> MxFp8Rows:
+    """:func:`mx_quantize` of bf16 rows [M, K] (K % 128 == 0) with row-major scales: the same
+    bytes and exponents, bit for bit.  GPU: quant.hip quant_mx_rows_kernel; CPU: the torch rule."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.shape[1] % 128 or h.shape[0] < 1:
+        raise ValueError(f"quant_mx_rows: bf16 [M, K] with K % 128 == 0, got {tuple(h.shape)} "
+                         f"{h.dtype}")
+    if not _gpu(h):
+        m = mx_quantize(h)
+        return MxFp8Rows(m.q, (m.exponents() + 127).to(torch.uint8).contiguous())
+    M, K = h.shape
+    q = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=h.device)
+    sc = torch.empty(M, K // 128, dtype=torch.uint8, device=h.device)
+    native().quant_mx_rows(q, sc, h.contiguous())
+    return MxFp8Rows(q, sc)
+
+
 FP4_MAX_KTILES = 128  # k-tiles one split of gemm_fp4 may own (gemm_fp4.hip kMaxKt: its LDS slot)
 
 
@@ -1426,6 +1460,7 @@ MoERouting = ref.MoERouting
 ExpertWeights = ref.ExpertWeights
 MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
 MOE_MAX_TOPK = ref.MOE_MAX_TOPK
+MOE_TILE_MX_MAX_K = 16384  # moe_tile_mx.hip kMaxKt * 128: the activation scales' LDS slot
 moe_tile_capacity = ref.moe_tile_capacity
 
 
@@ -1498,11 +1533,20 @@ def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
     return bool(rows and torch.device(device).type == "cuda" and T * k >= rows * E)
 
 
-def moe_grouped_gemm(x: torch.Tensor, w, r: MoERouting, down: bool = False,
+def moe_uses_mx(T: int, k: int, E: int, weight_format: str, device) -> bool:
+    """Whether that call runs on the block-scaled fp4 x fp8 tile GEMM (moe_tile_mx.hip, MX fp8
+    activations): it goes to the tiles (:func:`moe_uses_tiles`), ``KernelPolicy.moe_tile_mx`` is
+    set and the experts are MXFP4."""
+    return bool(weight_format == "mxfp4" and policy().moe_tile_mx
+                and moe_uses_tiles(T, k, E, weight_format, device))
+
+
+def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
                      w_scale: Optional[torch.Tensor] = None,
                      w_block_scale: Optional[torch.Tensor] = None,
-                     tiles: Optional[bool] = None) -> torch.Tensor:
+                     tiles: Optional[bool] = None,
+                     mx: Optional[bool] = None) -> torch.Tensor:
     """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
     ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
     rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
@@ -1522,7 +1566,18 @@ def moe_grouped_gemm(x: torch.Tensor, w, r: MoERouting, down: bool = False,
     ``tiles=True`` on them is a ``ValueError``).  The quantised tile kernels widen the weights
     exactly to bf16 and run the bf16 tile kernel's MFMAs in its order: MXFP4 gives its result on
     the dequantised weights bit for bit, fp8 the same up to the row scale applied to the fp32
-    sum.  The CPU path ignores ``tiles``."""
+    sum.  The CPU path ignores ``tiles``.
+
+    ``mx`` (MXFP4 experts): True quantises the activations to MX fp8 with row-major scales
+    (:func:`quant_mx_rows`; ``x`` may also be an :class:`MxFp8Rows` already) and multiplies them
+    with the weight nibbles on the block-scaled MFMA (moe_tile_mx.hip): N % 128 == 0,
+    K % 128 == 0, K <= 16384, and ``KernelPolicy.moe_tile_rows_q`` set, as for ``tiles=True``;
+    anything else is a ``ValueError``, never another kernel.  The numerics are those of
+    ``dequantize(mx_quantize(x)) @ dequantize_mxfp4(w)^T`` in fp32 with the same epilogue
+    rounding, which is what ``mx=True`` computes on the CPU.  None lets :func:`moe_uses_mx`
+    decide (``KernelPolicy.moe_tile_mx``, off by default); False never uses that kernel."""
+    if isinstance(x, MxFp8Rows) and mx is not True:
+        raise ValueError("moe_grouped_gemm: MxFp8Rows activations go with mx=True")
     if isinstance(w, ExpertWeights):
         if w_scale is not None or w_block_scale is not None:
             raise ValueError("moe_grouped_gemm: ExpertWeights carry their scale; w_scale / "
@@ -1550,8 +1605,30 @@ def moe_grouped_gemm(x: torch.Tensor, w, r: MoERouting, down: bool = False,
                              "weights' device")
         if w.shape[2] % 64:
             raise ValueError("moe_grouped_gemm: needs K % 128 == 0")
+    dev = x.q.device if isinstance(x, MxFp8Rows) else x.device
     if out is None:
-        out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=x.device)
+        out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=dev)
+    if mx is None:
+        mx = tiles is not False and moe_uses_mx(T, k, e.E, e.format, dev)
+    if mx:
+        if tiles is False:
+            raise ValueError("moe_grouped_gemm: mx=True runs on the tiles; tiles=False excludes it")
+        if e.format != "mxfp4":
+            raise ValueError(f"moe_grouped_gemm: mx=True needs MXFP4 expert weights, got "
+                             f"{e.format} (bf16 and fp8 experts keep bf16 activations)")
+        if N % 128 or e.K % 128 or e.K > MOE_TILE_MX_MAX_K:
+            raise ValueError(f"moe_grouped_gemm: mx=True needs N % 128 == 0 and K % 128 == 0, "
+                             f"K <= {MOE_TILE_MX_MAX_K}; got N={N}, K={e.K}")
+        a = x if isinstance(x, MxFp8Rows) else quant_mx_rows(x)
+        if dev.type != "cuda":
+            return ref.moe_grouped_gemm(a.dequantize(), e, r, 1 if down else 0, out)
+        if not policy().moe_tile_rows_q:
+            raise ValueError("moe_grouped_gemm: mx=True needs KernelPolicy.moe_tile_rows_q set "
+                             "(with it at 0 quantised experts run on the weight-streaming kernel)")
+        native().moe_tile_gemm_mx(out, a.q.contiguous(), a.sc.contiguous(), w, r.sorted_pairs,
+                                  r.expert_count, r.expert_offset, T, k, 1 if down else 0,
+                                  scale.contiguous())
+        return out
     if not _gpu(x):
         ok = (w.dtype == torch.uint8 or
               (w.dtype == torch.bfloat16 if scale is None else

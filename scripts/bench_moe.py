@@ -67,7 +67,12 @@ weights) and ``moe_tile_bf16`` (the bf16 tile kernel on the dequantised weights,
 does the quantised kernel follow its bytes?), plus the two products alone on each kernel.
 ``vs_bf16_tile`` is the time ratio of a quantised tile candidate to its bf16 twin and
 ``weight_bytes_vs_bf16`` the ratio of the expert bytes behind it.  Results:
-``<out>/moe_tile_fp8.json`` / ``<out>/moe_tile_fp4.json``.
+``<out>/moe_tile_fp8.json`` / ``<out>/moe_tile_fp4.json``.  ``--tile --fp4`` also times the
+block-scaled kernel (csrc/kernels/moe_tile_mx.hip) in the same interleaved rounds: ``moe_tile_mx``
+(route, quantise x, gate|up, quantise h, down, combine), ``gate_up_tile_mx`` / ``down_tile_mx`` on
+activations quantised beforehand, ``quant_x`` / ``quant_h`` (the quantiser passes alone), with
+``vs_tile`` = time / the widening MXFP4 tile kernel's; the run is also kept as
+``<out>/moe_tile_mx.json``.
 """
 import argparse
 import os
@@ -376,15 +381,16 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
         hit = hit_total / copies
         touched = hit * 3 * H * I * 2 * byte_ratio    # expert bytes one layer streams
 
-        def moe_with(tiles, bf16=False):
+        def moe_with(tiles, bf16=False, mx=False):
             def run(c):
                 r = ops.moe_route(logits[c], k, spec.norm_topk_prob)
                 if bf16:
                     h = ops.moe_grouped_gemm(x, wgu[c], r, tiles=tiles)
                     y = ops.moe_grouped_gemm(h, wd[c], r, down=True, tiles=tiles)
-                else:
-                    h = ops.moe_grouped_gemm(x, qgu[c], r, tiles=tiles, **{kw: sgu[c]})
-                    y = ops.moe_grouped_gemm(h, qd[c], r, down=True, tiles=tiles, **{kw: sd[c]})
+                else:       # mx: both quantiser passes (x once per token, h sorted) are inside
+                    h = ops.moe_grouped_gemm(x, qgu[c], r, tiles=tiles, mx=mx, **{kw: sgu[c]})
+                    y = ops.moe_grouped_gemm(h, qd[c], r, down=True, tiles=tiles, mx=mx,
+                                             **{kw: sd[c]})
                 return ops.moe_combine(y, r.topk_w)
             return run
 
@@ -399,6 +405,8 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
         err = {n: (f(0).float() - ref).abs().max().item()
                for n, f in (("moe", moe_with(False)), ("moe_tile", moe_with(True)),
                             ("moe_tile_bf16", moe_with(True, bf16=True)))}
+        if a.fp4:
+            err["moe_tile_mx"] = (moe_with(True, mx=True)(0).float() - ref).abs().max().item()
         hs = [ops.moe_grouped_gemm(x, qgu[c], routes[c], tiles=False, **{kw: sgu[c]})
               for c in range(copies)]
         ys = [ops.moe_grouped_gemm(hs[c], qd[c], routes[c], down=True, tiles=False, **{kw: sd[c]})
@@ -414,6 +422,18 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
             x, wgu[c], routes[c], out=hs[c], tiles=True)
         cands["down_tile_bf16"] = lambda c: ops.moe_grouped_gemm(
             hs[c], wd[c], routes[c], down=True, out=ys[c], tiles=True)
+        if a.fp4:   # the block-scaled kernel (moe_tile_mx.hip): the block, its products on
+            # activations quantised beforehand, and the two quantiser passes alone
+            xq = ops.quant_mx_rows(x)
+            hq = [ops.quant_mx_rows(hs[c]) for c in range(copies)]
+            hm = [hs[c].clone() for c in range(copies)]
+            cands["moe_tile_mx"] = moe_with(True, mx=True)
+            cands["gate_up_tile_mx"] = lambda c: ops.moe_grouped_gemm(
+                xq, qgu[c], routes[c], out=hm[c], mx=True, **{kw: sgu[c]})
+            cands["down_tile_mx"] = lambda c: ops.moe_grouped_gemm(
+                hq[c], qd[c], routes[c], down=True, out=ys[c], mx=True, **{kw: sd[c]})
+            cands["quant_x"] = lambda c: ops.quant_mx_rows(x).q
+            cands["quant_h"] = lambda c: ops.quant_mx_rows(hm[c]).q
         graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
                   for n, f in cands.items()}
         samples = {n: [] for n in cands}
@@ -431,10 +451,12 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
                "max_abs_loop": round(ref.abs().max().item(), 3)}
         for n in cands:
             us = statistics.median(samples[n])
-            base = n.replace("_tile_bf16", "").replace("_tile", "").replace("loop", "moe")
+            base = (n.replace("_mx", "").replace("_tile_bf16", "").replace("_tile", "")
+                    .replace("loop", "moe"))
             row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
-                      "max_us": round(max(samples[n]), 2),
-                      "TFLOPs": round(flop[base] / us / 1e6, 1)}
+                      "max_us": round(max(samples[n]), 2)}
+            if base in flop:                          # the quantiser passes have none
+                row[n]["TFLOPs"] = round(flop[base] / us / 1e6, 1)
         for n in ("moe", "gate_up", "down"):
             t, s, b = row[n + "_tile"], row[n], row[n + "_tile_bf16"]
             t["vs_" + n] = round(t["us"] / s["us"], 3)
@@ -443,6 +465,16 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
             t["vs_bf16_tile"] = round(t["us"] / b["us"], 3)
             t["separated_from_bf16_tile"] = bool(t["max_us"] < b["min_us"]
                                                  or b["max_us"] < t["min_us"])
+        if a.fp4:   # against the widening MXFP4 tile kernel of the same run
+            for n in ("moe", "gate_up", "down"):
+                m, t = row[n + "_tile_mx"], row[n + "_tile"]
+                m["vs_tile"] = round(m["us"] / t["us"], 3)
+                m["separated"] = bool(m["max_us"] < t["min_us"] or t["max_us"] < m["min_us"])
+            print(f"{name:14s} mx  T={T:5d} moe_tile_mx {row['moe_tile_mx']['us']:10.1f} us "
+                  f"(x{row['moe_tile_mx']['vs_tile']:.3f} of moe_tile, sep "
+                  f"{row['moe_tile_mx']['separated']})  gate_up {row['gate_up_tile_mx']['us']:.1f} "
+                  f"down {row['down_tile_mx']['us']:.1f}  quant x {row['quant_x']['us']:.1f} "
+                  f"h {row['quant_h']['us']:.1f}", flush=True)
         row["moe_tile"]["vs_loop"] = round(row["moe_tile"]["us"] / row["loop"]["us"], 3)
         row["moe"]["vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
         res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
@@ -456,6 +488,8 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
               f"(bf16 {row['gate_up_tile_bf16']['us']:.1f})  down {row['down']['us']:.1f} -> "
               f"{row['down_tile']['us']:.1f} (bf16 {row['down_tile_bf16']['us']:.1f})", flush=True)
         bm._save(a, f"moe_tile_{fmt}.json", res)
+        if a.fp4:   # the same run, kept as the block-scaled kernel's record
+            bm._save(a, "moe_tile_mx.json", res)
         del graphs
         torch.cuda.empty_cache()
     del qgu, sgu, qd, sd, wgu, wd
@@ -630,6 +664,12 @@ def main():
             "moe_tile": f"the same launches with both products on the {fmt} MFMA tile GEMM "
                         "(128-row tiles, moe_tile.hip; the weights widened at fragment-read time)",
             "moe_tile_bf16": "the bf16 tile GEMM on the dequantised weights",
+            **({"moe_tile_mx": "route, quantise x to MX fp8 (row-major scales), gate|up, quantise "
+                               "h, down on the block-scaled fp4 x fp8 MFMA (moe_tile_mx.hip), "
+                               "combine; vs_tile = time / moe_tile's in the same run",
+                "gate_up_tile_mx / down_tile_mx, quant_x / quant_h":
+                    "its two products on activations quantised beforehand, and the two "
+                    "quantiser passes alone"} if a.fp4 else {}),
             "loop": "per hit expert on the dequantised bf16 weights: index_select, F.linear, "
                     "swiglu, F.linear, index_add_ (fp32); routing on the host, not timed",
             "gate_up / down, gate_up_tile / down_tile, gate_up_tile_bf16 / down_tile_bf16":
