@@ -727,6 +727,14 @@ class KernelPolicy:
     # "Sparse MoE: block-scaled tile GEMM").  bf16 and fp8 experts ignore it, and so does every
     # call that moe_tile_rows_q leaves on the weight-streaming kernel
     moe_tile_mx: bool = False
+    # sparse MoE, fp8 experts: where moe_tile_rows_q sends them to the tiles, run both products
+    # on the block-scaled MFMA with both operands fp8 (csrc/kernels/moe_tile_f8.hip; x and h
+    # quantised to MX fp8 with row-major scales first, the weight's fp32 row scale applied in the
+    # epilogue) instead of widening the weight to bf16.  Experimental and off: it changes the
+    # numerics of those products (fp8 activation rounding; docs/kernels.md "Sparse MoE:
+    # block-scaled tile GEMM, fp8 experts").  bf16 and MXFP4 experts ignore it, and so does every
+    # call that moe_tile_rows_q leaves on the weight-streaming kernel
+    moe_tile_f8: bool = False
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 

@@ -257,6 +257,17 @@ int launch_moe_tile_gemm_mx(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, 
                             const int* sorted_pairs, const int* expert_count,
                             const int* expert_offset, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream);
+// The same two products for fp8 experts on the block-scaled MFMA with both operands fp8
+// (moe_tile_f8.hip): the stored e4m3 weight bytes times MX fp8 activations (a_q / a_sc as above,
+// gathered the same way), the activation scales on the MFMA's scale operand, the fp32 row scale
+// W.scale [E, N] applied to the fp32 sum in the epilogue before any rounding.  W.format must be
+// kExpertFp8 (else -6); N % 128 == 0, K % 128 == 0, K <= moe_tile_f8_max_k() (else -2); grid and
+// other codes as above
+int moe_tile_f8_max_k();
+int launch_moe_tile_gemm_f8(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
+                            const int* sorted_pairs, const int* expert_count,
+                            const int* expert_offset, int T, int E, int k, int N, int K,
+                            int epilogue, hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);

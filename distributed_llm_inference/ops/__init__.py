@@ -1461,6 +1461,7 @@ ExpertWeights = ref.ExpertWeights
 MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
 MOE_MAX_TOPK = ref.MOE_MAX_TOPK
 MOE_TILE_MX_MAX_K = 16384  # moe_tile_mx.hip kMaxKt * 128: the activation scales' LDS slot
+MOE_TILE_F8_MAX_K = 16384  # moe_tile_f8.hip kMaxKt * 128: the same slot
 moe_tile_capacity = ref.moe_tile_capacity
 
 
@@ -1541,6 +1542,14 @@ def moe_uses_mx(T: int, k: int, E: int, weight_format: str, device) -> bool:
                 and moe_uses_tiles(T, k, E, weight_format, device))
 
 
+def moe_uses_f8(T: int, k: int, E: int, weight_format: str, device) -> bool:
+    """Whether that call runs on the block-scaled fp8 x fp8 tile GEMM (moe_tile_f8.hip, MX fp8
+    activations): it goes to the tiles (:func:`moe_uses_tiles`), ``KernelPolicy.moe_tile_f8`` is
+    set and the experts are fp8."""
+    return bool(weight_format == "fp8" and policy().moe_tile_f8
+                and moe_uses_tiles(T, k, E, weight_format, device))
+
+
 def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
                      w_scale: Optional[torch.Tensor] = None,
@@ -1568,14 +1577,17 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     the dequantised weights bit for bit, fp8 the same up to the row scale applied to the fp32
     sum.  The CPU path ignores ``tiles``.
 
-    ``mx`` (MXFP4 experts): True quantises the activations to MX fp8 with row-major scales
-    (:func:`quant_mx_rows`; ``x`` may also be an :class:`MxFp8Rows` already) and multiplies them
-    with the weight nibbles on the block-scaled MFMA (moe_tile_mx.hip): N % 128 == 0,
-    K % 128 == 0, K <= 16384, and ``KernelPolicy.moe_tile_rows_q`` set, as for ``tiles=True``;
-    anything else is a ``ValueError``, never another kernel.  The numerics are those of
-    ``dequantize(mx_quantize(x)) @ dequantize_mxfp4(w)^T`` in fp32 with the same epilogue
-    rounding, which is what ``mx=True`` computes on the CPU.  None lets :func:`moe_uses_mx`
-    decide (``KernelPolicy.moe_tile_mx``, off by default); False never uses that kernel."""
+    ``mx`` (MXFP4 and fp8 experts): True quantises the activations to MX fp8 with row-major
+    scales (:func:`quant_mx_rows`; ``x`` may also be an :class:`MxFp8Rows` already) and multiplies
+    them with the weights as they are stored on the block-scaled MFMA -- MXFP4 nibbles with both
+    scale sets on the instruction (moe_tile_mx.hip), fp8 bytes with the fp32 row scale applied to
+    the fp32 sum in the epilogue (moe_tile_f8.hip): N % 128 == 0, K % 128 == 0, K <= 16384, and
+    ``KernelPolicy.moe_tile_rows_q`` set, as for ``tiles=True``; anything else is a
+    ``ValueError``, never another kernel.  The numerics are those of
+    ``dequantize(mx_quantize(x))`` times the dequantised weights (fp8: the bytes, then the row
+    scale) in fp32 with the same epilogue rounding, which is what ``mx=True`` computes on the
+    CPU.  None lets :func:`moe_uses_mx` (``KernelPolicy.moe_tile_mx``) and :func:`moe_uses_f8`
+    (``KernelPolicy.moe_tile_f8``) decide, both off by default; False never uses those kernels."""
     if isinstance(x, MxFp8Rows) and mx is not True:
         raise ValueError("moe_grouped_gemm: MxFp8Rows activations go with mx=True")
     if isinstance(w, ExpertWeights):
@@ -1609,25 +1621,32 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     if out is None:
         out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=dev)
     if mx is None:
-        mx = tiles is not False and moe_uses_mx(T, k, e.E, e.format, dev)
+        mx = tiles is not False and (moe_uses_mx(T, k, e.E, e.format, dev)
+                                     or moe_uses_f8(T, k, e.E, e.format, dev))
     if mx:
         if tiles is False:
             raise ValueError("moe_grouped_gemm: mx=True runs on the tiles; tiles=False excludes it")
-        if e.format != "mxfp4":
-            raise ValueError(f"moe_grouped_gemm: mx=True needs MXFP4 expert weights, got "
-                             f"{e.format} (bf16 and fp8 experts keep bf16 activations)")
-        if N % 128 or e.K % 128 or e.K > MOE_TILE_MX_MAX_K:
+        if e.format not in ("mxfp4", "fp8"):
+            raise ValueError(f"moe_grouped_gemm: mx=True needs MXFP4 or fp8 expert weights, got "
+                             f"{e.format} (bf16 experts keep bf16 activations)")
+        f8 = e.format == "fp8"
+        if f8 and (w.dtype != FP8 or scale is None or scale.dtype != torch.float32
+                   or tuple(scale.shape) != (w.shape[0], N) or scale.device != w.device):
+            raise ValueError("moe_grouped_gemm: fp8 e4m3fn weights go with w_scale fp32 [E, N] "
+                             "on the weights' device")
+        max_k = MOE_TILE_F8_MAX_K if f8 else MOE_TILE_MX_MAX_K
+        if N % 128 or e.K % 128 or e.K > max_k:
             raise ValueError(f"moe_grouped_gemm: mx=True needs N % 128 == 0 and K % 128 == 0, "
-                             f"K <= {MOE_TILE_MX_MAX_K}; got N={N}, K={e.K}")
+                             f"K <= {max_k}; got N={N}, K={e.K}")
         a = x if isinstance(x, MxFp8Rows) else quant_mx_rows(x)
         if dev.type != "cuda":
             return ref.moe_grouped_gemm(a.dequantize(), e, r, 1 if down else 0, out)
         if not policy().moe_tile_rows_q:
             raise ValueError("moe_grouped_gemm: mx=True needs KernelPolicy.moe_tile_rows_q set "
                              "(with it at 0 quantised experts run on the weight-streaming kernel)")
-        native().moe_tile_gemm_mx(out, a.q.contiguous(), a.sc.contiguous(), w, r.sorted_pairs,
-                                  r.expert_count, r.expert_offset, T, k, 1 if down else 0,
-                                  scale.contiguous())
+        gemm = native().moe_tile_gemm_f8 if f8 else native().moe_tile_gemm_mx
+        gemm(out, a.q.contiguous(), a.sc.contiguous(), w, r.sorted_pairs, r.expert_count,
+             r.expert_offset, T, k, 1 if down else 0, scale.contiguous())
         return out
     if not _gpu(x):
         ok = (w.dtype == torch.uint8 or

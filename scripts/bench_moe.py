@@ -72,7 +72,9 @@ block-scaled kernel (csrc/kernels/moe_tile_mx.hip) in the same interleaved round
 (route, quantise x, gate|up, quantise h, down, combine), ``gate_up_tile_mx`` / ``down_tile_mx`` on
 activations quantised beforehand, ``quant_x`` / ``quant_h`` (the quantiser passes alone), with
 ``vs_tile`` = time / the widening MXFP4 tile kernel's; the run is also kept as
-``<out>/moe_tile_mx.json``.
+``<out>/moe_tile_mx.json``.  ``--tile --fp8`` does the same for the fp8 x fp8 block-scaled kernel
+(csrc/kernels/moe_tile_f8.hip): ``moe_tile_f8``, ``gate_up_tile_f8`` / ``down_tile_f8``, ``quant_x``
+/ ``quant_h``, ``vs_tile`` against the widening fp8 tile kernel, kept as ``<out>/moe_tile_f8.json``.
 """
 import argparse
 import os
@@ -336,6 +338,7 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
     H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
                   spec.num_experts_per_tok)
     fmt = "fp4" if a.fp4 else "fp8"
+    bs = "mx" if a.fp4 else "f8"      # the format's block-scaled kernel: moe_tile_mx / moe_tile_f8
     kw = "w_block_scale" if a.fp4 else "w_scale"
     quantise = ops.quantize_expert_weights_mxfp4 if a.fp4 else ops.quantize_expert_weights_fp8
     copies = 8 if E * 3 * H * I * 2 < (2 << 30) else 3   # bench_model's rule, on the bf16 bytes
@@ -405,8 +408,7 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
         err = {n: (f(0).float() - ref).abs().max().item()
                for n, f in (("moe", moe_with(False)), ("moe_tile", moe_with(True)),
                             ("moe_tile_bf16", moe_with(True, bf16=True)))}
-        if a.fp4:
-            err["moe_tile_mx"] = (moe_with(True, mx=True)(0).float() - ref).abs().max().item()
+        err["moe_tile_" + bs] = (moe_with(True, mx=True)(0).float() - ref).abs().max().item()
         hs = [ops.moe_grouped_gemm(x, qgu[c], routes[c], tiles=False, **{kw: sgu[c]})
               for c in range(copies)]
         ys = [ops.moe_grouped_gemm(hs[c], qd[c], routes[c], down=True, tiles=False, **{kw: sd[c]})
@@ -422,18 +424,18 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
             x, wgu[c], routes[c], out=hs[c], tiles=True)
         cands["down_tile_bf16"] = lambda c: ops.moe_grouped_gemm(
             hs[c], wd[c], routes[c], down=True, out=ys[c], tiles=True)
-        if a.fp4:   # the block-scaled kernel (moe_tile_mx.hip): the block, its products on
-            # activations quantised beforehand, and the two quantiser passes alone
-            xq = ops.quant_mx_rows(x)
-            hq = [ops.quant_mx_rows(hs[c]) for c in range(copies)]
-            hm = [hs[c].clone() for c in range(copies)]
-            cands["moe_tile_mx"] = moe_with(True, mx=True)
-            cands["gate_up_tile_mx"] = lambda c: ops.moe_grouped_gemm(
-                xq, qgu[c], routes[c], out=hm[c], mx=True, **{kw: sgu[c]})
-            cands["down_tile_mx"] = lambda c: ops.moe_grouped_gemm(
-                hq[c], qd[c], routes[c], down=True, out=ys[c], mx=True, **{kw: sd[c]})
-            cands["quant_x"] = lambda c: ops.quant_mx_rows(x).q
-            cands["quant_h"] = lambda c: ops.quant_mx_rows(hm[c]).q
+        # the block-scaled kernel (moe_tile_mx.hip / moe_tile_f8.hip): the block, its products on
+        # activations quantised beforehand, and the two quantiser passes alone
+        xq = ops.quant_mx_rows(x)
+        hq = [ops.quant_mx_rows(hs[c]) for c in range(copies)]
+        hm = [hs[c].clone() for c in range(copies)]
+        cands["moe_tile_" + bs] = moe_with(True, mx=True)
+        cands["gate_up_tile_" + bs] = lambda c: ops.moe_grouped_gemm(
+            xq, qgu[c], routes[c], out=hm[c], mx=True, **{kw: sgu[c]})
+        cands["down_tile_" + bs] = lambda c: ops.moe_grouped_gemm(
+            hq[c], qd[c], routes[c], down=True, out=ys[c], mx=True, **{kw: sd[c]})
+        cands["quant_x"] = lambda c: ops.quant_mx_rows(x).q
+        cands["quant_h"] = lambda c: ops.quant_mx_rows(hm[c]).q
         graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
                   for n, f in cands.items()}
         samples = {n: [] for n in cands}
@@ -451,7 +453,7 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
                "max_abs_loop": round(ref.abs().max().item(), 3)}
         for n in cands:
             us = statistics.median(samples[n])
-            base = (n.replace("_mx", "").replace("_tile_bf16", "").replace("_tile", "")
+            base = (n.replace("_" + bs, "").replace("_tile_bf16", "").replace("_tile", "")
                     .replace("loop", "moe"))
             row[n] = {"us": round(us, 2), "min_us": round(min(samples[n]), 2),
                       "max_us": round(max(samples[n]), 2)}
@@ -465,16 +467,16 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
             t["vs_bf16_tile"] = round(t["us"] / b["us"], 3)
             t["separated_from_bf16_tile"] = bool(t["max_us"] < b["min_us"]
                                                  or b["max_us"] < t["min_us"])
-        if a.fp4:   # against the widening MXFP4 tile kernel of the same run
-            for n in ("moe", "gate_up", "down"):
-                m, t = row[n + "_tile_mx"], row[n + "_tile"]
-                m["vs_tile"] = round(m["us"] / t["us"], 3)
-                m["separated"] = bool(m["max_us"] < t["min_us"] or t["max_us"] < m["min_us"])
-            print(f"{name:14s} mx  T={T:5d} moe_tile_mx {row['moe_tile_mx']['us']:10.1f} us "
-                  f"(x{row['moe_tile_mx']['vs_tile']:.3f} of moe_tile, sep "
-                  f"{row['moe_tile_mx']['separated']})  gate_up {row['gate_up_tile_mx']['us']:.1f} "
-                  f"down {row['down_tile_mx']['us']:.1f}  quant x {row['quant_x']['us']:.1f} "
-                  f"h {row['quant_h']['us']:.1f}", flush=True)
+        for n in ("moe", "gate_up", "down"):   # against the widening tile kernel of the same run
+            m, t = row[f"{n}_tile_{bs}"], row[n + "_tile"]
+            m["vs_tile"] = round(m["us"] / t["us"], 3)
+            m["separated"] = bool(m["max_us"] < t["min_us"] or t["max_us"] < m["min_us"])
+        blk = row["moe_tile_" + bs]
+        print(f"{name:14s} {bs}  T={T:5d} moe_tile_{bs} {blk['us']:10.1f} us "
+              f"(x{blk['vs_tile']:.3f} of moe_tile, sep {blk['separated']})  gate_up "
+              f"{row['gate_up_tile_' + bs]['us']:.1f} (x{row['gate_up_tile_' + bs]['vs_tile']:.3f})  "
+              f"down {row['down_tile_' + bs]['us']:.1f} (x{row['down_tile_' + bs]['vs_tile']:.3f})  "
+              f"quant x {row['quant_x']['us']:.1f} h {row['quant_h']['us']:.1f}", flush=True)
         row["moe_tile"]["vs_loop"] = round(row["moe_tile"]["us"] / row["loop"]["us"], 3)
         row["moe"]["vs_loop"] = round(row["moe"]["us"] / row["loop"]["us"], 3)
         res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
@@ -488,8 +490,7 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
               f"(bf16 {row['gate_up_tile_bf16']['us']:.1f})  down {row['down']['us']:.1f} -> "
               f"{row['down_tile']['us']:.1f} (bf16 {row['down_tile_bf16']['us']:.1f})", flush=True)
         bm._save(a, f"moe_tile_{fmt}.json", res)
-        if a.fp4:   # the same run, kept as the block-scaled kernel's record
-            bm._save(a, "moe_tile_mx.json", res)
+        bm._save(a, f"moe_tile_{bs}.json", res)   # the same run, the block-scaled kernel's record
         del graphs
         torch.cuda.empty_cache()
     del qgu, sgu, qd, sd, wgu, wd
@@ -669,7 +670,13 @@ def main():
                                "combine; vs_tile = time / moe_tile's in the same run",
                 "gate_up_tile_mx / down_tile_mx, quant_x / quant_h":
                     "its two products on activations quantised beforehand, and the two "
-                    "quantiser passes alone"} if a.fp4 else {}),
+                    "quantiser passes alone"} if a.fp4 else
+               {"moe_tile_f8": "route, quantise x to MX fp8 (row-major scales), gate|up, quantise "
+                               "h, down on the block-scaled fp8 x fp8 MFMA (moe_tile_f8.hip), "
+                               "combine; vs_tile = time / moe_tile's in the same run",
+                "gate_up_tile_f8 / down_tile_f8, quant_x / quant_h":
+                    "its two products on activations quantised beforehand, and the two "
+                    "quantiser passes alone"}),
             "loop": "per hit expert on the dequantised bf16 weights: index_select, F.linear, "
                     "swiglu, F.linear, index_add_ (fp32); routing on the host, not timed",
             "gate_up / down, gate_up_tile / down_tile, gate_up_tile_bf16 / down_tile_bf16":
