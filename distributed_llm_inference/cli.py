@@ -43,6 +43,10 @@ def _common(ap: argparse.ArgumentParser) -> None:
     wq.add_argument("--fp8-experts", action="store_true",
                     help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
                          "attention, norms, the router, dense layers and a shared expert stay bf16")
+    wq.add_argument("--fp8-block-experts", action="store_true",
+                    help="sparse-MoE models: fp8-e4m3 expert weights with one scale per 16 weight "
+                         "rows and 128 input features (what 128x128 block-scaled FP8 checkpoints "
+                         "hold: their default, no flag needed); the rest stays bf16")
     wq.add_argument("--fp4-experts", action="store_true",
                     help="sparse-MoE models: MXFP4 expert weights (4-bit e2m1 + e8m0 scale per 32: "
                          "17/32 byte per expert parameter); attention, norms and the router stay "
@@ -80,6 +84,7 @@ def engine_config(a):
     quantize = ("fp8" if a.fp8 else "int8" if a.int8
                 else "mxfp4" if getattr(a, "fp4", False)
                 else "fp8_experts" if getattr(a, "fp8_experts", False)
+                else "fp8_block_experts" if getattr(a, "fp8_block_experts", False)
                 else "mxfp4_experts" if getattr(a, "fp4_experts", False) else False)
     # sparse-MoE models take bf16 weights, fp8_experts or mxfp4_experts: fail here, before any rank
     # is started
@@ -126,6 +131,18 @@ def cmd_plan(a) -> int:
         per_layer = (spec.expert_param_count() + 4 * rows
                      + 2 * (spec.layer_param_count() - spec.expert_param_count()))
         per_param = per_layer / spec.layer_param_count()
+    block_fp8 = getattr(a, "fp8_block_experts", False) or (
+        spec.weight_quant == "fp8_block" and spec.num_experts
+        and not (a.fp8 or a.int8 or a.fp4 or a.fp8_experts or a.fp4_experts))
+    if block_fp8:
+        # experts: a byte per parameter and an fp32 scale per 16 stored rows and 128 k (a 128 x
+        # 128 FP8 checkpoint's tables expanded 8x along the rows); the rest of the layer stays bf16
+        if not spec.num_experts:
+            raise ValueError(f"--fp8-block-experts needs a sparse MoE model; {spec.name} has no "
+                             "experts")
+        per_layer = (spec.expert_param_count() + 4 * spec.expert_param_count() // (16 * 128)
+                     + 2 * (spec.layer_param_count() - spec.expert_param_count()))
+        per_param = per_layer / spec.layer_param_count()
     if getattr(a, "fp4_experts", False):
         # experts: K / 2 nibble bytes and K / 32 scale bytes per stored weight row (2 I gate|up
         # rows of K = H and H down rows of K = I per expert); the rest of the layer stays bf16
@@ -143,7 +160,8 @@ def cmd_plan(a) -> int:
         expert-only modes leave all of it bf16 (as they leave the shared expert)."""
         if not spec.num_experts or spec.is_sparse_layer(i):
             return per_layer
-        expert_mode = getattr(a, "fp8_experts", False) or getattr(a, "fp4_experts", False)
+        expert_mode = (getattr(a, "fp8_experts", False) or getattr(a, "fp4_experts", False)
+                       or block_fp8)
         return int(spec.layer_param_count(i) * (2 if expert_mode else per_param))
     replicas = []
     for r in range(layout.dp):

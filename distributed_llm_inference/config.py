@@ -79,6 +79,10 @@ class ModelSpec:
     # intermediate_size
     decoder_sparse_step: int = 1
     mlp_only_layers: Tuple[int, ...] = ()
+    # how the checkpoint stores its linear weights: None (bf16 / fp16 / fp32 tensors) or
+    # "fp8_block" (HF quantization_config quant_method "fp8": e4m3 bytes with an fp32
+    # weight_scale_inv per 128 x 128 block)
+    weight_quant: Optional[str] = None
 
     def __post_init__(self):
         if self.num_experts == 0:
@@ -311,6 +315,7 @@ class ModelSpec:
         if isinstance(eos, list):
             eos = eos[0]
         return cls(
+            weight_quant=_parse_quantization_config(cfg.get("quantization_config")),
             arch="llama",
             vocab_size=cfg["vocab_size"],
             hidden_size=h,
@@ -376,6 +381,10 @@ class ModelSpec:
                          norm_topk_prob=self.norm_topk_prob, qkv_bias=self.attention_bias,
                          decoder_sparse_step=self.decoder_sparse_step,
                          mlp_only_layers=list(self.mlp_only_layers))
+        if self.weight_quant == "fp8_block":
+            extra["quantization_config"] = dict(quant_method="fp8", fmt="e4m3",
+                                                activation_scheme="dynamic",
+                                                weight_block_size=[128, 128])
         if self.model_type in ("qwen2", "qwen3", "qwen3_moe", "qwen2_moe"):
             extra.update(use_sliding_window=self.sliding_window is not None,
                          sliding_window=self.sliding_window)
@@ -496,22 +505,50 @@ PRESETS: Dict[str, ModelSpec] = {
 }
 
 
+def _parse_quantization_config(q: Any) -> Optional[str]:
+    """``ModelSpec.weight_quant`` of a HF ``quantization_config``: None without one, "fp8_block"
+    for exactly quant_method "fp8", e4m3, weight_block_size [128, 128]; anything else is refused
+    with the offending field named."""
+    if not q:
+        return None
+    if q.get("quant_method") != "fp8":
+        raise ValueError(f"quantization_config.quant_method={q.get('quant_method')!r}: only "
+                         "\"fp8\" (128 x 128 block-scaled e4m3) checkpoints are supported")
+    if q.get("fmt", "e4m3") != "e4m3":
+        raise ValueError(f"quantization_config.fmt={q.get('fmt')!r}: only \"e4m3\" is supported")
+    wbs = q.get("weight_block_size")
+    if wbs is None or list(wbs) != [128, 128]:
+        raise ValueError(f"quantization_config.weight_block_size={wbs!r}: only [128, 128] is "
+                         "supported (per-tensor fp8 checkpoints are not)")
+    return "fp8_block"
+
+
 def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
     """Whole-model weight quantisation of a sparse-MoE model is an error, not a fallback: the
     grouped expert GEMM (csrc/kernels/moe.hip) takes bf16 expert weights, or fp8 ones under the
-    mode of its own, "fp8_experts", or MXFP4 ones under "mxfp4_experts", which leave everything
-    but the experts bf16 -- and which a model without experts cannot take."""
-    if mode in ("fp8_experts", "mxfp4_experts") and not spec.num_experts:
+    mode of its own, "fp8_experts" (per-row scales) or "fp8_block_experts" (one scale per 16 rows
+    and 128 k), or MXFP4 ones under "mxfp4_experts", which leave everything but the experts bf16
+    -- and which a model without experts cannot take.  A block-scaled FP8 checkpoint
+    (``spec.weight_quant``) holds its experts in the "fp8_block_experts" format already: that mode
+    is its default, "bf16" dequantises everything, and the other quantising modes are refused."""
+    if mode in ("fp8_experts", "mxfp4_experts", "fp8_block_experts") and not spec.num_experts:
         raise ValueError(f"{mode} needs a sparse MoE model; {spec.name} ({spec.model_type}) "
                          "has no experts")
+    if spec.weight_quant and spec.num_experts and mode not in (False, None, "none", "bf16",
+                                                               "fp8_block_experts"):
+        mode = "fp8" if mode is True else mode
+        raise ValueError(f"{mode}: {spec.name} is a block-scaled FP8 checkpoint, whose experts "
+                         "load as fp8_block_experts (the default; \"bf16\" dequantises them); "
+                         "requantising them to another format is not supported")
     if spec.num_experts and mode not in (False, None, "none", "bf16", "fp8_experts",
-                                         "mxfp4_experts"):
+                                         "mxfp4_experts", "fp8_block_experts"):
         mode = "fp8" if mode is True else mode
         raise ValueError(f"{mode} weights are not supported for sparse MoE layers "
                          f"({spec.model_type}, {spec.name}): the grouped expert GEMM takes bf16 "
                          "expert weights, or fp8 expert weights as mode fp8_experts "
-                         "(--fp8-experts), or MXFP4 expert weights as mode mxfp4_experts "
-                         "(--fp4-experts)")
+                         "(--fp8-experts), block-scaled fp8 expert weights as mode "
+                         "fp8_block_experts (--fp8-block-experts), or MXFP4 expert weights as "
+                         "mode mxfp4_experts (--fp4-experts)")
 
 
 def resolve_model(model: Any) -> ModelSpec:

@@ -1168,8 +1168,9 @@ void moe_group(Tensor ids, Tensor expert_count, Tensor expert_offset, Tensor sor
 
 // The routed experts' weights with the scale that goes with them, the format inferred from w's
 // dtype: bf16 [E, N, K] without a scale; fp8 e4m3fn [E, N, K] with w_scale fp32 [E, N] (one per
-// weight row); uint8 MXFP4 nibbles [E, N, K / 2] with w_block_scale uint8 [E, N, K / 32] (e8m0,
-// one per 32 k).  K is the logical reduction length
+// weight row) or fp32 [E, N / 16, K / 128] (block-scaled: one per 16 stored rows and 128 k);
+// uint8 MXFP4 nibbles [E, N, K / 2] with w_block_scale uint8 [E, N, K / 32] (e8m0, one per 32 k).
+// K is the logical reduction length
 struct ExpertArgs {
   dli::ExpertW w;
   int64_t E, N, K;
@@ -1189,6 +1190,15 @@ ExpertArgs check_expert_weights(const char* what, const Tensor& w, const optiona
     TORCH_CHECK(w_scale.has_value() && w_scale->scalar_type() == at::kFloat, what,
                 ": fp8 e4m3fn expert weights go with an fp32 w_scale (bf16 expert weights only "
                 "go without a scale)");
+    if (w_scale->dim() == 3) {   // block-scaled: the scale's rank tells the two fp8 formats apart
+      const int64_t K = w.size(2);
+      TORCH_CHECK(N % 16 == 0 && K >= 128 && K % 128 == 0, what,
+                  ": block-scaled fp8 expert weights need N % 16 == 0 and K % 128 == 0");
+      TORCH_CHECK(w_scale->size(0) == E && w_scale->size(1) == N / 16 &&
+                      w_scale->size(2) == K / 128 && w_scale->device() == dev,
+                  what, ": block scale fp32 [E, N / 16, K / 128] on the weights' device");
+      return {{w.data_ptr(), w_scale->data_ptr(), dli::kExpertFp8Block}, E, N, K};
+    }
     TORCH_CHECK(w_scale->dim() == 2 && w_scale->size(0) == E && w_scale->size(1) == N &&
                     w_scale->device() == dev, what, ": w_scale [E, N] on the weights' device");
     return {{w.data_ptr(), w_scale->data_ptr(), dli::kExpertFp8}, E, N, w.size(2)};
@@ -1330,7 +1340,7 @@ void moe_tile_gemm_f8(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sort
   CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
   const ExpertArgs e = check_expert_weights("moe_tile_gemm_f8", w, scale, a_q.device());
   TORCH_CHECK(e.w.format == dli::kExpertFp8, "moe_tile_gemm_f8: fp8 expert weights only (e4m3fn "
-              "with an fp32 w_scale); MXFP4 experts run on moe_tile_gemm_mx, bf16 experts on "
+              "with an fp32 w_scale [E, N]; block-scaled fp8 experts run on moe_tile_gemm); MXFP4 experts run on moe_tile_gemm_mx, bf16 experts on "
               "moe_tile_gemm");
   TORCH_CHECK(out.dim() == 2 && a_q.dim() == 2 && a_q.element_size() == 1,
               "moe_tile_gemm_f8: out 2-D, a_q = e4m3 bytes [R, K]");

@@ -212,15 +212,19 @@ int launch_moe_topk_shared(int* ids, float* w, float* shared_w, const bf16* logi
 int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int* sorted_pairs,
                      int* tile_expert, int* tile_start, int* tile_rows, int* n_tiles, int T, int E,
                      int k, int cap, hipStream_t stream);
-// The routed experts' weights in one of three formats (`format` is an ExpertFormat):
+// The routed experts' weights in one of four formats (`format` is an ExpertFormat):
 //   bf16:  w [E, N, K] bf16, scale null;
 //   fp8:   w [E, N, K] e4m3fn bytes, scale [E, N] fp32 (one per weight row, in the rows' stored
 //          order), applied to the fp32 accumulator;
 //   MXFP4: w [E, N, K / 2] e2m1 nibbles (element 2 j in the low nibble of byte j), scale
 //          [E, N, K / 32] e8m0 bytes (one per 32 k of a stored weight row), spent in the exact
-//          widening to bf16: no epilogue scale.
+//          widening to bf16: no epilogue scale;
+//   block-scaled fp8 (the hub's 128 x 128 FP8 checkpoints): w [E, N, K] e4m3fn bytes, scale
+//          [E, N / 16, K / 128] fp32, one per 16 consecutive stored rows and 128 consecutive k
+//          (a checkpoint's 128-row block is eight such groups), applied inside the k-loop to
+//          the fp32 sum of each 128-k block: no epilogue scale.  K % 128 == 0.
 // The activations stay bf16.  A quantised format with a null scale is -5, an unknown format -6.
-enum ExpertFormat { kExpertBf16 = 0, kExpertFp8 = 1, kExpertFp4 = 2 };
+enum ExpertFormat { kExpertBf16 = 0, kExpertFp8 = 1, kExpertFp4 = 2, kExpertFp8Block = 3 };
 struct ExpertW {
   const void* w;
   const void* scale;
@@ -235,7 +239,7 @@ int launch_moe_grouped_gemm(bf16* out, const bf16* x, ExpertW W, const int* sort
                             int epilogue, hipStream_t stream);
 // Grouped MFMA tile GEMM for experts with many rows (moe_tile.hip): the products of
 // launch_moe_grouped_gemm (the same two epilogues, x and out as there) on tiles of <= 128 rows x
-// 128 weight rows staged in LDS; N % 128 == 0, K % 64 == 0 (MXFP4: K % 128 == 0).  The 128-row
+// 128 weight rows staged in LDS; N % 128 == 0, K % 64 == 0 (MXFP4, block-scaled fp8: K % 128 == 0).  The 128-row
 // tiles are derived in the kernel from expert_count [E] / expert_offset [E + 1]
 // (launch_moe_group's); the grid is (N / 128, moe_tile_gemm_capacity) = min(E, P) + P / 128 row
 // tiles.  Quantised bytes are staged in LDS and widened exactly to bf16 when a fragment is read,

@@ -19,9 +19,9 @@
 //     expert's range is cut into tiles of <= 32 rows; at most min(E, P) + P / 32 tiles exist.
 //     Ids are clamped into [0, E), so the counts always sum to P and nothing is written outside
 //     the tables.
-//   * moe_grouped_gemm.  The small kernels' product, wstream_core.h's, on the experts' weights
-//     (the operand layouts of the three formats, x through LDS, the K split over the 8 waves and
-//     the load pipeline are described there).  Grid (N / 32, tile capacity); workgroup (nb, tile)
+//   * moe_grouped_gemm (the kernel template is in moe_grouped.h).  The small kernels' product,
+//     wstream_core.h's, on the experts' weights (the operand layouts of the formats, x through
+//     LDS, the K split over the 8 waves and the load pipeline are described there).  Grid (N / 32, tile capacity); workgroup (nb, tile)
 //     multiplies the <= 32 rows of its tile with rows 32 nb .. 32 nb + 31 of its tile's expert:
 //     the weight rows are loaded as they are (N % 32 == 0), the x rows through the tile's table
 //     (below; image rows past the tile's count repeat its last row).  A tile index >= n_tiles
@@ -49,6 +49,13 @@
 //     the MFMAs are the bf16 variant's, so the result is the bf16 kernel's on the dequantised
 //     weights bit for bit.  The scale is spent in the widening: nothing is left for the epilogue,
 //     and the activations are never quantised.
+//     Block-scaled fp8 weights (WF = kMoeFp8Block: W8 [E, N, K] e4m3fn bytes, scale
+//     [E, N / 16, K / 128] fp32, one per 16 stored rows and 128 k -- the hub's 128 x 128 FP8
+//     checkpoints, a 128-row block being eight 16-row groups): the scale changes with every
+//     k-step, so the four MFMAs of a step and A tile run into a zeroed step accumulator which is
+//     added, times the tile's scale of that step, to the running sum (wstream_core.h).  Nothing is
+//     left for the epilogue.  The kernel template (moe_grouped.h) is instantiated for this format
+//     in moe_fp8_block.hip.
 //   * moe_combine.  out[t] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order.
 //
 // Shared expert (Qwen2-MoE): every token of a sparse layer also runs one dense SwiGLU expert, on
@@ -64,14 +71,11 @@
 //   * moe_combine<true>: out[t] = bf16(sum_slot w[t, slot] * y[t k + slot] + shared_w[t] * s[t]),
 //     fp32, the slots in order, then the shared term, then the one rounding; the vector width,
 //     the guard and the launch shape are moe_combine<false>'s.
-#include "wstream_core.h"
+#include "moe_grouped.h"
 
 namespace dli {
 
 namespace {
-
-constexpr int kMaxExperts = 256;
-constexpr int kMaxTopK = 8;
 
 // ------------------------------------------------------------------------------------- top-k
 constexpr int kTopkWaves = 4;
@@ -213,122 +217,6 @@ moe_group_kernel(const int* __restrict__ ids, int* __restrict__ expert_count,
   }
 }
 
-// ------------------------------------------------------------------------------------- grouped GEMM
-constexpr int kTileRows = 32;          // activation rows per tile: two 16-column B tiles
-
-enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
-enum MoeWf { kMoeBf16 = kWsBf16, kMoeFp8 = kWsFp8, kMoeFp4 = kWsFp4 };
-
-// k-steps of weight loads in flight per lane: 8 (bf16) / 4 (fp8) 16-byte loads per step, 16
-// loads in flight either way (fp8 with 2 measured 0-4 % slower: docs/kernels.md); fp4 has 2
-// 16-byte loads and 2 scale bytes per step: 4 + 4 in flight with 2, which measured 0-7 % faster
-// than 4 and 8 at 1-16 rows and 4-5 % slower than 4 at Mixtral's 128 / 512 rows (docs/kernels.md)
-template <int WF> constexpr int kUnrollOf = WF == kMoeFp8 ? 4 : 2;
-
-__device__ __forceinline__ int clamp_pair(int p, int P) { return min(max(p, 0), P - 1); }
-
-// One tile: `rows` (1 .. 16 MT) activation rows x the 32 weight rows n0 .. n0 + 31 of W [N, K].
-// pairs = sorted_pairs + start.  W is the expert's [N, K] bf16 (WF = kMoeBf16), e4m3 bytes with
-// its N row scales `wscale` (fp32, kMoeFp8) or [N, K / 2] MXFP4 bytes with its [N, K / 32] e8m0
-// block scales `wscale` (bytes, kMoeFp4).
-template <int MT, int EPI, int WF>
-__device__ __forceinline__ void moe_tile(char* smem, const bf16* __restrict__ x,
-                                         const char* __restrict__ W,
-                                         const void* __restrict__ wscale, bf16* __restrict__ out,
-                                         const int* __restrict__ pairs, int start, int rows,
-                                         int nb, int topk, int P, int N, int K) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int n0 = nb * kWsRowsWg;
-
-  // N % 32 == 0: both A tiles are whole.  Image rows past `rows` repeat the tile's last row.
-  f32x4 acc[2][MT];
-  if (!ws_accumulate<MT, WF, kUnrollOf<WF>>(
-          smem, x, W, static_cast<const uint8_t*>(wscale), n0, K, [](int n) { return n; },
-          [&](int row) {
-            const int tr = min(row, rows - 1);
-            if constexpr (EPI == kMoeGateUp)
-              return (size_t)(clamp_pair(pairs[tr], P) / topk);   // token
-            else
-              return (size_t)(start + tr);   // h row
-          },
-          acc))
-    return;
-
-  // ---- epilogue: acc[a][b][e] = y[m = 16 b + r][n = n0 + 16 a + 4 g + e] ----
-  if constexpr (WF == kMoeFp8) {   // the scales of the lane's four weight rows per A tile
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const f32x4 ws = *reinterpret_cast<const f32x4*>(static_cast<const float*>(wscale) + n0 +
-                                                       16 * a + 4 * g);
-#pragma unroll
-      for (int b = 0; b < MT; ++b)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[a][b][e] *= ws[e];
-    }
-  }
-  if constexpr (EPI == kMoeGateUp) {
-    const int I = N >> 1;
-    const int col = 16 * nb + 4 * g;
-#pragma unroll
-    for (int b = 0; b < MT; ++b) {
-      const int m = 16 * b + r;
-      if (m >= rows) continue;
-      bf16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float gt = (float)(bf16)acc[0][b][e];
-        const float up = (float)(bf16)acc[1][b][e];
-        o[e] = (bf16)(silu(gt) * up);
-      }
-      *reinterpret_cast<bf16x4*>(out + (size_t)(start + m) * I + col) = o;
-    }
-  } else {
-#pragma unroll
-    for (int b = 0; b < MT; ++b) {
-      const int m = 16 * b + r;
-      if (m >= rows) continue;
-      const size_t dst = (size_t)clamp_pair(pairs[m], P);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)acc[a][b][e];
-        *reinterpret_cast<bf16x4*>(out + dst * N + n0 + 16 * a + 4 * g) = o;
-      }
-    }
-  }
-}
-
-template <int EPI, int WF>
-__global__ void __launch_bounds__(kWsThreads)
-moe_grouped_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ W,
-                        const void* __restrict__ wscale, bf16* __restrict__ out,
-                        const int* __restrict__ sorted_pairs,
-                        const int* __restrict__ tile_expert, const int* __restrict__ tile_start,
-                        const int* __restrict__ tile_rows, const int* __restrict__ n_tiles,
-                        int E, int topk, int P, int N, int K) {
-  __shared__ __attribute__((aligned(1024))) char smem[kWsSmem<kTileRows / 16>];
-  const int tile = blockIdx.y, nb = blockIdx.x;
-  if (tile >= n_tiles[0]) return;   // before any DMA or barrier
-  const int e = min(max(tile_expert[tile], 0), E - 1);
-  const int rows = min(max(tile_rows[tile], 1), min(kTileRows, P));
-  const int start = min(max(tile_start[tile], 0), P - rows);
-  // expert e's weights and scales: N rows of 2 K (bf16), K (fp8) or K / 2 (fp4) bytes; N fp32
-  // row scales (fp8) or N K / 32 block-scale bytes (fp4)
-  const size_t wrow = WF == kMoeFp4 ? (size_t)(K >> 1) : (size_t)K * (WF == kMoeFp8 ? 1 : 2);
-  const char* We = static_cast<const char*>(W) + (size_t)e * N * wrow;
-  const void* se = nullptr;
-  if constexpr (WF == kMoeFp8) se = static_cast<const float*>(wscale) + (size_t)e * N;
-  if constexpr (WF == kMoeFp4)
-    se = static_cast<const uint8_t*>(wscale) + (size_t)e * N * (size_t)(K >> 5);
-  const int* pairs = sorted_pairs + start;
-  if (rows <= 16)
-    moe_tile<1, EPI, WF>(smem, x, We, se, out, pairs, start, rows, nb, topk, P, N, K);
-  else
-    moe_tile<2, EPI, WF>(smem, x, We, se, out, pairs, start, rows, nb, topk, P, N, K);
-}
-
 // ------------------------------------------------------------------------------------- combine
 // kShared: shared [T, H] (bf16) times shared_w [T] is added after the k slots
 template <bool kShared>
@@ -399,40 +287,12 @@ int launch_moe_group(const int* ids, int* expert_count, int* expert_offset, int*
   return 0;
 }
 
-namespace {
-
-template <int WF>
-int launch_grouped(bf16* out, const bf16* x, const void* W, const void* wscale,
-                   const int* sorted_pairs, const int* tile_expert, const int* tile_start,
-                   const int* tile_rows, const int* n_tiles, int cap, int T, int E, int k, int N,
-                   int K, int epilogue, hipStream_t stream) {
-  if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK) return -1;
-  if (N <= 0 || N % 32 != 0 || K <= 0 || K % 128 != 0) return -2;
-  if (cap <= 0 || cap > 65535 || (long)T * k > (1L << 30)) return -3;
-  if (out == nullptr || x == nullptr || W == nullptr) return -5;
-  if (WF != kMoeBf16 && wscale == nullptr) return -5;
-  const dim3 grid(N / kWsRowsWg, cap);
-  const int P = T * k;
-  if (epilogue == kMoeGateUp)
-    moe_grouped_gemm_kernel<kMoeGateUp, WF><<<grid, kWsThreads, 0, stream>>>(
-        x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
-        K);
-  else if (epilogue == kMoeDown)
-    moe_grouped_gemm_kernel<kMoeDown, WF><<<grid, kWsThreads, 0, stream>>>(
-        x, W, wscale, out, sorted_pairs, tile_expert, tile_start, tile_rows, n_tiles, E, k, P, N,
-        K);
-  else
-    return -4;
-  return 0;
-}
-
-}  // namespace
-
 int launch_moe_grouped_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                             const int* tile_expert, const int* tile_start, const int* tile_rows,
                             const int* n_tiles, int cap, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream) {
-  static_assert(kMoeBf16 == kExpertBf16 && kMoeFp8 == kExpertFp8 && kMoeFp4 == kExpertFp4);
+  static_assert(kMoeBf16 == kExpertBf16 && kMoeFp8 == kExpertFp8 && kMoeFp4 == kExpertFp4 &&
+                kMoeFp8Block == kExpertFp8Block);
   switch (W.format) {
     case kExpertBf16:
       return launch_grouped<kMoeBf16>(out, x, W.w, nullptr, sorted_pairs, tile_expert, tile_start,
@@ -443,6 +303,10 @@ int launch_moe_grouped_gemm(bf16* out, const bf16* x, ExpertW W, const int* sort
     case kExpertFp4:
       return launch_grouped<kMoeFp4>(out, x, W.w, W.scale, sorted_pairs, tile_expert, tile_start,
                                      tile_rows, n_tiles, cap, T, E, k, N, K, epilogue, stream);
+    case kExpertFp8Block:   // moe_fp8_block.hip
+      return launch_moe_grouped_fp8_block(out, x, W.w, W.scale, sorted_pairs, tile_expert,
+                                          tile_start, tile_rows, n_tiles, cap, T, E, k, N, K,
+                                          epilogue, stream);
   }
   return -6;
 }

@@ -56,6 +56,14 @@
 //     buffer, then waits for all but those 4 MT newest operations (vmcnt counts in issue order).
 //     kWsFp4: the scale bytes are vector memory loads too, issued with the weight loads, i.e.
 //     before the next x -- so "all but the 4 MT newest" still covers them.
+//   * kWsFp8Block: kWsFp8's bytes with one fp32 scale per 16 weight rows and 128 k,
+//     bscale[(n0 + 16 a) / 16][t] -- one per A tile and k-step, an arbitrary fp32, so it cannot be
+//     spent in the widening and cannot wait for the epilogue.  The four MFMAs of a step and A tile
+//     run into a zeroed accumulator `part`, and acc += scale * part follows on the vector ALU
+//     (4 MT fused multiply-adds per A tile and step).  The scale is a 4-byte vector load from an
+//     address that is the same in the 64 lanes, issued with the weight loads like the fp4 scale
+//     bytes, so the counted waits cover it too.  Every product of the step meets in fp32 before
+//     the scale: the result is the fp32 sum over the blocks of scale * (exact block sum).
 //   * result.  C/D: lane (c, g) holds D[n = 4 g + e][m = c], e = 0..3 -- four consecutive output
 //     columns of activation row c: acc[a][b][e] = y[m = 16 b + r][n = n0 + 16 a + 4 g + e].
 #pragma once
@@ -68,7 +76,7 @@ constexpr int kWsWaves = 8;              // K-split ways = waves per workgroup
 constexpr int kWsThreads = kWsWaves * 64;
 constexpr int kWsRowsWg = 32;            // weight rows per workgroup: two 16-row A tiles
 
-enum WsFormat { kWsBf16 = 0, kWsFp8 = 1, kWsFp4 = 2 };
+enum WsFormat { kWsBf16 = 0, kWsFp8 = 1, kWsFp4 = 2, kWsFp8Block = 3 };
 
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));   // nontemporal-loadable 16 B
 
@@ -84,7 +92,8 @@ template <int MT> constexpr int kWsSmem = kWsWaves * 2 * (MT * 16 * 256);
 
 // The K-split product of one workgroup: activation image rows 0 .. 16 MT - 1 (image row i is row
 // xrow(i) of x [*, K]) times the weight rows wrow(n0) .. wrow(n0 + 31) of W (rows of 2 K (kWsBf16),
-// K (kWsFp8) or K / 2 (kWsFp4) bytes; bscale: the [*, K / 32] e8m0 block scales, kWsFp4 only).
+// K (kWsFp8, kWsFp8Block) or K / 2 (kWsFp4) bytes; bscale: the [*, K / 32] e8m0 block scales
+// (kWsFp4) or the [* / 16, K / 128] fp32 block scales (kWsFp8Block), else unused).
 // K % 128 == 0; smem holds kWsSmem<MT> bytes, 1024-aligned.  Every wave of the workgroup must
 // call it (it holds a barrier); it returns true in wave 0, with the sum over K in `sum`, and false
 // in the others, which are done.
@@ -118,6 +127,9 @@ __device__ __forceinline__ bool ws_accumulate(char* smem, const bf16* __restrict
     if constexpr (WF == kWsFp4) {
       wp[a] = W + n * (size_t)(K >> 1) + 16 * g;
       sp[a] = bscale + n * (size_t)(K >> 5) + g;
+    } else if constexpr (WF == kWsFp8Block) {   // the fp32 scale of the row's 16-row group, step 0
+      wp[a] = W + n * K + 32 * g;
+      sp[a] = bscale + (n >> 4) * (size_t)(K >> 7) * 4;
     } else {
       wp[a] = W + (n * K + 32 * g) * kWB;
       sp[a] = nullptr;
@@ -153,6 +165,8 @@ __device__ __forceinline__ bool ws_accumulate(char* smem, const bf16* __restrict
         wv[a][i] = __builtin_nontemporal_load(
             reinterpret_cast<const u32x4w*>(wp[a] + (size_t)t * kStepB + 16 * i));
       if constexpr (WF == kWsFp4) sc[a] = sp[a][(size_t)t * 4];
+      if constexpr (WF == kWsFp8Block)   // fp32 bits: one address per A tile, the same in 64 lanes
+        sc[a] = *reinterpret_cast<const unsigned*>(sp[a] + (size_t)t * 4);
     }
   };
   auto stage_x = [&](int t, int buf) {
@@ -171,18 +185,35 @@ __device__ __forceinline__ bool ws_accumulate(char* smem, const bf16* __restrict
     for (int a = 0; a < 2; ++a) {
       float s = 0.f;   // kWsFp4: 2^(byte - 127), byte in [1, 254]
       if constexpr (WF == kWsFp4) s = __uint_as_float(sc[a] << 23);
+      if constexpr (WF == kWsFp8Block) s = __uint_as_float(sc[a]);
+      f32x4 part[MT];   // kWsFp8Block: this step's product, before its scale
+      if constexpr (WF == kWsFp8Block) {
+#pragma unroll
+        for (int b = 0; b < MT; ++b) part[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         bf16x8 wf;
         if constexpr (WF == kWsFp4)   // dword i of the lane's 4: exact widening
           wf = fp4x8_to_bf16x8(wv[a][0][i], s);
-        else if constexpr (WF == kWsFp8)   // dwords 2 i, 2 i + 1 of the lane's 8: exact widening
+        else if constexpr (WF == kWsFp8 || WF == kWsFp8Block)   // dwords 2 i, 2 i + 1 of the lane's 8
+                                                                // (exact widening)
           wf = fp8x8_to_bf16x8(uint2{wv[a][i >> 1][2 * (i & 1)], wv[a][i >> 1][2 * (i & 1) + 1]});
         else
           wf = __builtin_bit_cast(bf16x8, wv[a][i]);
 #pragma unroll
+        for (int b = 0; b < MT; ++b) {
+          if constexpr (WF == kWsFp8Block)
+            part[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb[b][i], part[b], 0, 0, 0);
+          else
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb[b][i], acc[a][b], 0, 0, 0);
+        }
+      }
+      if constexpr (WF == kWsFp8Block) {   // the step is one scale block along K
+#pragma unroll
         for (int b = 0; b < MT; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb[b][i], acc[a][b], 0, 0, 0);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[a][b][e] += s * part[b][e];
       }
     }
   };

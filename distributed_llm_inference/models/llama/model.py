@@ -117,6 +117,27 @@ class LlamaBlock(nn.Module):
                 layer.mlp.quantize_experts_fp8()
         return self
 
+    def quantize_experts_fp8_block(self) -> "LlamaBlock":
+        """Block-scaled fp8 (e4m3, one fp32 scale per 16 stored rows and 128 input features)
+        weights for the routed experts of every sparse-MoE layer; experts loaded from a 128 x 128
+        block-scaled FP8 checkpoint are in this format already and are left as they are.
+        Everything else stays bf16, as under :meth:`quantize_experts_fp8`."""
+        if not self.config.num_experts:
+            raise ValueError(f"fp8_block_experts needs a sparse MoE model; {self.config.name} "
+                             f"({self.config.model_type}) has no experts")
+        for layer in self.layers:   # dense layers of a mixed stack have no experts: skipped
+            if layer.is_moe:
+                layer.mlp.quantize_experts_fp8_block()
+        return self
+
+    def dequantize_experts(self) -> "LlamaBlock":
+        """Block-scaled fp8 experts (a 128 x 128 FP8 checkpoint's) back to bf16, one rounding per
+        weight; experts in any other format are left as they are."""
+        for layer in self.layers:
+            if layer.is_moe and layer.mlp.is_fp8_block:
+                layer.mlp.dequantize_experts()
+        return self
+
     def quantize_experts_mxfp4(self) -> "LlamaBlock":
         """MXFP4 (e2m1, one e8m0 scale per 32 input features) weights for the routed experts of
         every sparse-MoE layer; attention projections, norms, the router, dense layers and the

@@ -287,7 +287,10 @@ class MoEMLP(nn.Module):
     ``w_gate_up [E, 2I, H]`` holds every expert's rows in ``ops.swiglu_interleave`` order, always
     (``set_fused_swiglu`` leaves them alone); ``w_down [E, H, I]``.  Expert weights are bf16, or after
     :meth:`quantize_experts_fp8` e4m3 with one fp32 scale per weight row (``w_gate_up_scale
-    [E, 2I]``, ``w_down_scale [E, H]``), or after :meth:`quantize_experts_mxfp4` MXFP4 nibbles
+    [E, 2I]``, ``w_down_scale [E, H]``), or after :meth:`quantize_experts_fp8_block` -- or loaded
+    from a 128 x 128 block-scaled FP8 checkpoint -- e4m3 with one fp32 scale per 16 stored rows and
+    128 input features (the same two buffers, 3-D: ``[E, 2I / 16, H / 128]``,
+    ``[E, H / 16, I / 128]``), or after :meth:`quantize_experts_mxfp4` MXFP4 nibbles
     ``[E, 2I, H / 2]`` / ``[E, H, I / 2]`` with one e8m0 scale per 32 input features
     (``w_gate_up_block_scale [E, 2I, H / 32]``, ``w_down_block_scale [E, H, I / 32]``); the router
     stays bf16 and the activations are never quantised.  The block returns a plain bf16 tensor:
@@ -339,6 +342,10 @@ class MoEMLP(nn.Module):
         return self.w_gate_up_scale is not None
 
     @property
+    def is_fp8_block(self) -> bool:
+        return self.is_fp8 and self.w_gate_up_scale.dim() == 3
+
+    @property
     def is_mxfp4(self) -> bool:
         return self.w_gate_up_block_scale is not None
 
@@ -353,7 +360,8 @@ class MoEMLP(nn.Module):
         """Expert weights -> ``fmt`` (ops.ExpertWeights.quantize: one expert at a time), in place
         of the bf16 tensors, which are freed.  A scale belongs to a stored gate|up row (MXFP4: to
         32 input features of it), so the rows are quantised in their interleaved order."""
-        have = "fp8" if self.is_fp8 else "mxfp4" if self.is_mxfp4 else "bf16"
+        have = ("fp8_block" if self.is_fp8_block else "fp8" if self.is_fp8
+                else "mxfp4" if self.is_mxfp4 else "bf16")
         if have == fmt:
             return
         if have != "bf16":
@@ -362,11 +370,24 @@ class MoEMLP(nn.Module):
         for name in ("w_gate_up", "w_down"):
             q = ops.ExpertWeights.quantize(getattr(self, name).data, fmt)
             setattr(self, name, nn.Parameter(q.w, requires_grad=False))
-            setattr(self, name + ("_scale" if fmt == "fp8" else "_block_scale"), q.scale)
+            setattr(self, name + ("_block_scale" if fmt == "mxfp4" else "_scale"), q.scale)
 
     def quantize_experts_fp8(self) -> None:
         """Expert weights -> fp8 e4m3 with per-row scales."""
         self._quantize_experts("fp8")
+
+    def quantize_experts_fp8_block(self) -> None:
+        """Expert weights -> fp8 e4m3 with one scale per 16 stored rows and 128 input features."""
+        self._quantize_experts("fp8_block")
+
+    def dequantize_experts(self) -> None:
+        """Quantised expert weights -> bf16 (``ExpertWeights.dequantize``, one expert at a time)."""
+        for name in ("w_gate_up", "w_down"):
+            q = self.experts(name)
+            w = torch.stack([q.dequantize(e) for e in range(q.E)])
+            setattr(self, name, nn.Parameter(w, requires_grad=False))
+            setattr(self, name + "_scale", None)
+            setattr(self, name + "_block_scale", None)
 
     def quantize_experts_mxfp4(self) -> None:
         """Expert weights -> MXFP4 nibbles with e8m0 block scales."""
@@ -394,7 +415,12 @@ class MoEMLP(nn.Module):
         (Qwen3-MoE ``mlp.experts.{e}.{gate,up,down}_proj.weight``, Mixtral
         ``block_sparse_moe.experts.{e}.{w1,w3,w2}.weight`` with w1 = gate, w3 = up, w2 = down), or
         the fused 3-D tensors ``experts.gate_up_proj [E, 2I, H]`` (gate half first) and
-        ``experts.down_proj [E, H, I]`` under either prefix."""
+        ``experts.down_proj [E, H, I]`` under either prefix.
+
+        Block-scaled FP8 checkpoints (per-expert keys whose ``weight`` is e4m3fn, each with a
+        ``weight_scale_inv [ceil(out / 128), ceil(in / 128)]`` fp32 sibling) load as ``"fp8_block"``
+        experts: the bytes are stored as they are, gate|up rows interleaved, and every 128-row
+        scale block is repeated over its 16-row groups -- no bf16 round trip."""
         if self.is_fp8:
             raise RuntimeError("MoEMLP.load_hf on fp8 experts: load the bf16 weights first, then "
                                "quantize_experts_fp8()")
@@ -433,10 +459,52 @@ class MoEMLP(nn.Module):
             return
         names = ("w1", "w3", "w2") if pre + "experts.0.w1.weight" in sd else (
             "gate_proj", "up_proj", "down_proj")
+        if f"{pre}experts.0.{names[0]}.weight_scale_inv" in sd:
+            return self._load_fp8_block(sd, pre, names)
         for e in range(self.num_experts):
             gate, up, down = (g(f"{pre}experts.{e}.{n}.weight") for n in names)
             self.w_gate_up[e].copy_(ops.swiglu_interleave(torch.cat([gate, up], 0)).to(dt))
             self.w_down[e].copy_(down.to(dt))
+
+    def _load_fp8_block(self, sd: dict, pre: str, names) -> None:
+        """The experts of a 128 x 128 block-scaled FP8 checkpoint (raw tensors of ``sd``)."""
+        E, I, H = self.num_experts, self.intermediate_size, self.gate.in_features
+        if I % 128 or H % 128:   # K % 128 == 0 for both products (and 2I % 256: the interleave)
+            raise ValueError(f"block-scaled fp8 experts need intermediate and hidden sizes that "
+                             f"are multiples of 128, got {I} and {H}")
+        dev = self.w_gate_up.device
+        f8 = torch.float8_e4m3fn
+        gu8 = torch.empty(E, 2 * I, H, dtype=f8, device=dev)
+        d8 = torch.empty(E, H, I, dtype=f8, device=dev)
+        gus = torch.empty(E, 2 * I // 16, H // 128, dtype=torch.float32, device=dev)
+        ds = torch.empty(E, H // 16, I // 128, dtype=torch.float32, device=dev)
+        src = ops._swiglu_src(2 * I, "cpu")
+
+        def take(e, n, rows, cols):
+            """(bytes [rows, cols], scales expanded to [rows / 16, cols / 128])"""
+            key = f"{pre}experts.{e}.{n}.weight"
+            if key not in sd or key + "_scale_inv" not in sd:
+                raise KeyError(f"missing weight {key} or its weight_scale_inv")
+            w, s = sd[key], sd[key + "_scale_inv"]
+            if w.dtype != f8 or tuple(w.shape) != (rows, cols):
+                raise ValueError(f"{key}: expected e4m3fn [{rows}, {cols}], got {w.dtype} "
+                                 f"{tuple(w.shape)}")
+            if tuple(s.shape) != (rows // 128, cols // 128):
+                raise ValueError(f"{key}_scale_inv: expected [{rows // 128}, {cols // 128}] for "
+                                 f"weight_block_size [128, 128], got {tuple(s.shape)}")
+            return w, s.float().repeat_interleave(8, 0)
+
+        for e in range(E):
+            (g8, gs), (u8, us), (w8, ws) = (take(e, n, *shp) for n, shp in zip(
+                names, ((I, H), (I, H), (H, I))))
+            # bytes are moved as bytes (no arithmetic on e4m3); 16 stored rows are 16 consecutive
+            # rows of one projection, so group j of the stored order is group src[16 j] / 16
+            gu8[e] = torch.cat([g8, u8], 0).view(torch.uint8)[src].view(f8)
+            gus[e] = torch.cat([gs, us], 0)[src[::16] // 16]
+            d8[e], ds[e] = w8, ws
+        self.w_gate_up = nn.Parameter(gu8, requires_grad=False)
+        self.w_down = nn.Parameter(d8, requires_grad=False)
+        self.w_gate_up_scale, self.w_down_scale = gus, ds
 
     def hf_dict(self) -> dict:
         """The hub's per-expert layout (inverse of :meth:`load_hf`); fp8 experts as their
@@ -461,6 +529,23 @@ class MoEMLP(nn.Module):
             for n, w in zip(names, (gate, up, down.dequantize(e))):
                 sd[f"{pre}experts.{e}.{n}.weight"] = w
         return sd
+
+
+def dequantize_fp8_block_weight(name: str, w8: torch.Tensor, scale_inv: torch.Tensor):
+    """A linear weight of a 128 x 128 block-scaled FP8 checkpoint as bf16: ``w8 [out, in]`` e4m3fn
+    times ``scale_inv [ceil(out / 128), ceil(in / 128)]`` (fp32), the product formed in fp32 and
+    rounded to bf16 once.  Not exact: the fp32 product of an e4m3 value and an fp32 scale has up to
+    27 significant bits, bf16 keeps 8.  Used for everything but the routed experts (attention
+    projections, a shared expert, dense MLP layers), which this project runs in bf16."""
+    out, inn = w8.shape
+    if w8.dtype != torch.float8_e4m3fn or tuple(scale_inv.shape) != ((out + 127) // 128,
+                                                                     (inn + 127) // 128):
+        raise ValueError(f"{name}: block-scaled fp8 needs e4m3fn [{out}, {inn}] with "
+                         f"weight_scale_inv [{(out + 127) // 128}, {(inn + 127) // 128}] "
+                         f"(weight_block_size [128, 128]), got {w8.dtype} and "
+                         f"{tuple(scale_inv.shape)}")
+    s = scale_inv.float().repeat_interleave(128, 0)[:out].repeat_interleave(128, 1)[:, :inn]
+    return (w8.float() * s).to(torch.bfloat16)
 
 
 class LlamaDecoderLayer(nn.Module):
@@ -568,6 +653,8 @@ class LlamaDecoderLayer(nn.Module):
         def g(k):
             if k not in sd:
                 raise KeyError(f"parameter {k} not found in state dict for layer {self.layer_idx}")
+            if k + "_scale_inv" in sd:   # a 128 x 128 block-scaled FP8 checkpoint's linear
+                return dequantize_fp8_block_weight(k, sd[k], sd[k + "_scale_inv"])
             return sd[k]
         dt = self.input_layernorm.weight.dtype
         with torch.no_grad():

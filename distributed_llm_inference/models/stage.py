@@ -25,7 +25,13 @@ def apply_quantization(block, mode, threshold: float = 6.0):
     "fp8" (e4m3 weights, per-channel scales), "int8" (LLM.int8, outlier ``threshold``) or
     "mxfp4" / "fp4" (OCP MX 4-bit e2m1 weights, one e8m0 scale per 32 input features), or
     "fp8_experts" (sparse-MoE models: e4m3 expert weights with per-row scales, the rest bf16) or
-    "mxfp4_experts" (sparse-MoE models: MXFP4 expert weights, the rest bf16)."""
+    "mxfp4_experts" (sparse-MoE models: MXFP4 expert weights, the rest bf16), or
+    "fp8_block_experts" (sparse-MoE models: e4m3 expert weights with one scale per 16 stored rows
+    and 128 input features -- what a 128 x 128 block-scaled FP8 checkpoint loads as, so there the
+    mode changes nothing; on bf16 experts it quantises them).  "bf16" also dequantises experts
+    that were loaded from such a checkpoint; False / None / "none" leave them as loaded."""
+    if mode == "bf16" and hasattr(block, "dequantize_experts"):
+        return block.dequantize_experts()
     if mode in (False, None, "none", "bf16"):
         return block
     if mode is True or mode == "fp8":
@@ -47,8 +53,13 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise ValueError(f"mxfp4_experts needs a sparse MoE model; {type(block).__name__} "
                              "has no experts")
         return block.quantize_experts_mxfp4()
+    if mode == "fp8_block_experts":
+        if not hasattr(block, "quantize_experts_fp8_block"):
+            raise ValueError(f"fp8_block_experts needs a sparse MoE model; "
+                             f"{type(block).__name__} has no experts")
+        return block.quantize_experts_fp8_block()
     raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / "
-                     "fp8_experts / mxfp4_experts)")
+                     "fp8_experts / fp8_block_experts / mxfp4_experts)")
 
 
 def make_block(spec: ModelSpec, layer_ids, device=None, dtype=torch.bfloat16):
@@ -116,8 +127,8 @@ class CausalLMStage(nn.Module):
         """``mode``: False / None / "none"; True / "fp8" (e4m3, the MI355X default); "int8"
         (LLM.int8 with outlier ``threshold``); "mxfp4" / "fp4" (4-bit MX weights: the
         interactive-decode and capacity mode; the LM head and embeddings stay bf16);
-        "fp8_experts" / "mxfp4_experts" (sparse-MoE models: only the routed experts' weights
-        become e4m3 / MXFP4)."""
+        "fp8_experts" / "fp8_block_experts" / "mxfp4_experts" (sparse-MoE models: only the
+        routed experts' weights become e4m3 with row or block scales / MXFP4)."""
         apply_quantization(self.block, mode, threshold)
         return self
 

@@ -549,6 +549,27 @@ def quantize_expert_weights_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
     return w8, scale
 
 
+def quantize_expert_weights_fp8_block(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Offline block-scaled fp8 quantisation of stacked expert weights ``[E, N, K]`` (N % 16 == 0,
+    K % 128 == 0): one scale ``amax / 448`` per 16 consecutive stored rows and 128 consecutive
+    input features (gate|up rows after :func:`swiglu_interleave`), one expert at a time.  Returns
+    ``(w8 [E, N, K] e4m3fn, scale [E, N / 16, K / 128] fp32)`` -- the layout the hub's 128 x 128
+    FP8 checkpoints are expanded to at load."""
+    if w.dim() != 3 or w.shape[1] % ref.FP8_BLOCK_ROWS or w.shape[2] % ref.FP8_BLOCK_K:
+        raise ValueError(f"quantize_expert_weights_fp8_block: [E, N, K] with N % 16 == 0 and "
+                         f"K % 128 == 0, got {tuple(w.shape)}")
+    E, N, K = w.shape
+    gn, gk = N // ref.FP8_BLOCK_ROWS, K // ref.FP8_BLOCK_K
+    w8 = torch.empty(E, N, K, dtype=FP8, device=w.device)
+    scale = torch.empty(E, gn, gk, dtype=torch.float32, device=w.device)
+    for e in range(E):
+        b = w[e].float().reshape(gn, ref.FP8_BLOCK_ROWS, gk, ref.FP8_BLOCK_K)
+        s = b.abs().amax((1, 3)).clamp_min(1e-12) / FP8_MAX
+        w8[e] = (b / s[:, None, :, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8).reshape(N, K)
+        scale[e] = s
+    return w8, scale
+
+
 # MXFP4 (OCP MX v1.0): e2m1 elements, one e8m0 power-of-two scale per 32 consecutive k
 MXFP4_BLOCK = ref.MXFP4_BLOCK
 
@@ -1522,12 +1543,13 @@ def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
     """Whether a sparse-MoE call of T tokens, top-k of E experts runs its routed experts on the
     grouped MFMA tile GEMM (moe_tile.hip) instead of the weight-streaming kernel (moe.hip):
     the policy field of the experts' format is set -- ``KernelPolicy.moe_tile_rows`` for
-    ``weight_format`` "bf16", ``KernelPolicy.moe_tile_rows_q`` for "fp8" and "mxfp4" -- the call
+    ``weight_format`` "bf16", ``KernelPolicy.moe_tile_rows_q`` for "fp8", "fp8_block" and
+    "mxfp4" -- the call
     is on the GPU (``device``: the activations'), and the mean rows per expert reach that
     threshold, ``T k >= rows E``.  Host-known integers only: no device sync."""
     if weight_format == "bf16":
         rows = policy().moe_tile_rows
-    elif weight_format in ("fp8", "mxfp4"):
+    elif weight_format in ("fp8", "fp8_block", "mxfp4"):
         rows = policy().moe_tile_rows_q
     else:
         rows = 0
@@ -1563,7 +1585,11 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     ``y [P, H]`` with row j of h at row ``sorted_pairs[j]`` (the pair index).  ``out`` may have
     more than P rows; the rest are not touched.  With ``w_scale [E, N]`` (fp32) ``w`` is fp8
     e4m3fn (:func:`quantize_expert_weights_fp8`): the row scale multiplies the fp32 product, the
-    activations stay bf16.  With ``w_block_scale [E, N, K / 32]`` (uint8 e8m0) ``w`` is MXFP4
+    activations stay bf16.  With ``w_scale [E, N / 16, K / 128]`` (fp32, 3-D) ``w`` is block-scaled
+    fp8 (``"fp8_block"``, :func:`quantize_expert_weights_fp8_block` or a 128 x 128 FP8 checkpoint):
+    the scale of a 16-row group and 128-k block multiplies that block's fp32 sum inside the
+    kernels' k-loop (moe_fp8_block.hip, moe_tile_fp8_block.hip).
+    With ``w_block_scale [E, N, K / 32]`` (uint8 e8m0) ``w`` is MXFP4
     nibbles ``uint8 [E, N, K / 2]`` (:func:`quantize_expert_weights_mxfp4`), widened exactly to
     bf16 in the kernel: the product is the bf16 kernel's on the dequantised weights.  ``w`` may
     also be an :class:`ExpertWeights`, which carries its scale: then neither keyword is given.
@@ -1587,7 +1613,10 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     ``dequantize(mx_quantize(x))`` times the dequantised weights (fp8: the bytes, then the row
     scale) in fp32 with the same epilogue rounding, which is what ``mx=True`` computes on the
     CPU.  None lets :func:`moe_uses_mx` (``KernelPolicy.moe_tile_mx``) and :func:`moe_uses_f8`
-    (``KernelPolicy.moe_tile_f8``) decide, both off by default; False never uses those kernels."""
+    (``KernelPolicy.moe_tile_f8``) decide, both off by default; False never uses those kernels.
+    Block-scaled fp8 experts never run there (an arbitrary fp32 block scale cannot ride on the
+    MFMA's e8m0 scale operand): with ``moe_tile_f8`` set they run on the widening tile GEMM, and
+    ``mx=True`` on them is a ``ValueError``."""
     if isinstance(x, MxFp8Rows) and mx is not True:
         raise ValueError("moe_grouped_gemm: MxFp8Rows activations go with mx=True")
     if isinstance(w, ExpertWeights):
@@ -1628,7 +1657,8 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
             raise ValueError("moe_grouped_gemm: mx=True runs on the tiles; tiles=False excludes it")
         if e.format not in ("mxfp4", "fp8"):
             raise ValueError(f"moe_grouped_gemm: mx=True needs MXFP4 or fp8 expert weights, got "
-                             f"{e.format} (bf16 experts keep bf16 activations)")
+                             f"{e.format} (bf16 experts keep bf16 activations; block-scaled "
+                             f"fp8 experts run on the widening kernels)")
         f8 = e.format == "fp8"
         if f8 and (w.dtype != FP8 or scale is None or scale.dtype != torch.float32
                    or tuple(scale.shape) != (w.shape[0], N) or scale.device != w.device):
@@ -1651,10 +1681,11 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     if not _gpu(x):
         ok = (w.dtype == torch.uint8 or
               (w.dtype == torch.bfloat16 if scale is None else
-               w.dtype == FP8 and tuple(scale.shape) == (w.shape[0], N)))
+               w.dtype == FP8 and tuple(scale.shape) in (
+                   (w.shape[0], N), (w.shape[0], N // 16, w.shape[2] // 128))))
         if not ok:
             raise ValueError("moe_grouped_gemm: bf16 weights, or fp8 e4m3fn weights with "
-                             "w_scale [E, N]")
+                             "w_scale [E, N] or [E, N / 16, K / 128]")
         return ref.moe_grouped_gemm(x, e, r, 1 if down else 0, out)
     fmt = e.format
     if tiles is None:
@@ -1663,7 +1694,7 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
         raise ValueError(f"moe_grouped_gemm: tiles=True needs bf16 expert weights, got {fmt} "
                          "(quantised experts run on the weight-streaming kernel unless "
                          "KernelPolicy.moe_tile_rows_q is set)")
-    if fmt == "mxfp4":
+    if fmt in ("mxfp4", "fp8_block"):
         scale = scale.contiguous()
     if tiles:
         native().moe_tile_gemm(out, x.contiguous(), w, r.sorted_pairs, r.expert_count,
@@ -1706,7 +1737,7 @@ def moe_mlp(x: torch.Tensor, gate_logits: torch.Tensor, gate_up, down, k: int, r
     """Sparse MoE MLP of ``x [T, H]`` (bf16) given its router logits ``[T, E]``: route, gate|up +
     SwiGLU and down on the grouped GEMM, weighted combine.  ``gate_up [E, 2I, H]`` (each
     expert's rows in :func:`swiglu_interleave` order) and ``down [E, H, I]`` are
-    :class:`ExpertWeights` (bf16, fp8 with row scales or MXFP4 with block scales), or bare bf16
+    :class:`ExpertWeights` (bf16, fp8 with row or block scales, or MXFP4), or bare bf16
     tensors.
     Experts with many rows each run both products on the tile GEMM when their format's policy
     field is set (:func:`moe_uses_tiles`: ``moe_tile_rows`` for bf16, ``moe_tile_rows_q`` for fp8

@@ -462,10 +462,13 @@ class MoERouting(NamedTuple):
 
 class ExpertWeights(NamedTuple):
     """The routed experts' stacked weights with the scale their format needs; the format follows
-    from ``w``'s dtype:
+    from ``w``'s dtype (and, for e4m3fn, from the scale's rank):
 
     * ``"bf16"``: ``w [E, N, K]`` bf16, no scale;
     * ``"fp8"``: ``w [E, N, K]`` e4m3fn, ``scale [E, N]`` fp32, one per weight row;
+    * ``"fp8_block"``: ``w [E, N, K]`` e4m3fn, ``scale [E, N / 16, K / 128]`` fp32, one per 16
+      consecutive stored rows and 128 consecutive input features (the hub's 128 x 128
+      block-scaled FP8 checkpoints, a 128-row block repeated over its eight 16-row groups);
     * ``"mxfp4"``: ``w [E, N, K / 2]`` uint8 nibbles (element 2j in the low nibble of byte j),
       ``scale [E, N, K / 32]`` uint8 e8m0, one per 32 input features."""
 
@@ -479,6 +482,8 @@ class ExpertWeights(NamedTuple):
         if fmt is None:
             raise ValueError(f"expert weights are bf16, fp8 e4m3fn or uint8 MXFP4 nibbles, got "
                              f"{self.w.dtype}")
+        if fmt == "fp8" and self.scale is not None and self.scale.dim() == 3:
+            return "fp8_block"
         return fmt
 
     @property
@@ -496,8 +501,10 @@ class ExpertWeights(NamedTuple):
 
     def dequantize(self, e: int) -> torch.Tensor:
         """Expert e's weight as bf16: the tensor itself, the MXFP4 rows widened (exact), or the
-        fp8 rows times their scales in fp32, rounded once."""
+        fp8 rows times their (row or block) scales in fp32, rounded once."""
         fmt, w = self.format, self.w[e]
+        if fmt == "fp8_block":
+            return (w.float() * expand_fp8_block_scale(self.scale[e])).to(torch.bfloat16)
         if fmt == "mxfp4":
             from . import dequantize_mxfp4   # the GPU kernel for GPU tensors
             return dequantize_mxfp4(w, self.scale[e])
@@ -508,15 +515,27 @@ class ExpertWeights(NamedTuple):
     @classmethod
     def quantize(cls, w: torch.Tensor, fmt: str) -> "ExpertWeights":
         """bf16 ``w [E, N, K]`` in format ``fmt`` (``ops.quantize_expert_weights_fp8`` /
-        ``_mxfp4``: one expert at a time); ``"bf16"`` wraps ``w`` as it is."""
-        from . import quantize_expert_weights_fp8, quantize_expert_weights_mxfp4
+        ``_fp8_block`` / ``_mxfp4``: one expert at a time); ``"bf16"`` wraps ``w`` as it is."""
+        from . import (quantize_expert_weights_fp8, quantize_expert_weights_fp8_block,
+                       quantize_expert_weights_mxfp4)
         if fmt == "bf16":
             return cls(w)
         if fmt == "fp8":
             return cls(*quantize_expert_weights_fp8(w))
+        if fmt == "fp8_block":
+            return cls(*quantize_expert_weights_fp8_block(w))
         if fmt == "mxfp4":
             return cls(*quantize_expert_weights_mxfp4(w))
-        raise ValueError(f"ExpertWeights.quantize: format bf16, fp8 or mxfp4, got {fmt!r}")
+        raise ValueError(f"ExpertWeights.quantize: format bf16, fp8, fp8_block or mxfp4, got "
+                         f"{fmt!r}")
+
+
+FP8_BLOCK_ROWS, FP8_BLOCK_K = 16, 128   # the stored scale groups of "fp8_block" experts
+
+
+def expand_fp8_block_scale(scale: torch.Tensor) -> torch.Tensor:
+    """``scale [..., N / 16, K / 128]`` -> the fp32 factor of every weight, ``[..., N, K]``."""
+    return scale.float().repeat_interleave(FP8_BLOCK_ROWS, -2).repeat_interleave(FP8_BLOCK_K, -1)
 
 
 def moe_tile_capacity(T: int, E: int, k: int, tile_rows: int = MOE_TILE_ROWS) -> int:
@@ -591,18 +610,20 @@ def moe_grouped_gemm(x: torch.Tensor, w: ExpertWeights, r: MoERouting, epilogue:
     """``epilogue`` 0: ``out[j] = swiglu(x[sorted_pairs[j] // k] . w[e]^T)`` for the rows j of
     expert e (``w [E, 2I, H]``, rows in ``ops.swiglu_interleave`` order); 1:
     ``out[sorted_pairs[j]] = x[j] . w[e]^T`` (``w [E, H, I]``).  fp32 products, one rounding.
-    Expert e is ``w.dequantize(e)``, except that fp8 rows times their scales stay fp32 (no
-    rounding to bf16 in between)."""
+    Expert e is ``w.dequantize(e)``, except that fp8 rows times their row or block scales stay
+    fp32 (no rounding to bf16 in between)."""
     k = r.topk_ids.shape[1]
     off = r.expert_offset.tolist()
     pairs = r.sorted_pairs.long()
-    fp8 = w.format == "fp8"
+    fmt = w.format
     for e in range(w.E):
         a, b = off[e], off[e + 1]
         if a == b:
             continue
-        if fp8:
+        if fmt == "fp8":
             wf = w.w[e].float() * w.scale[e].float()[:, None]
+        elif fmt == "fp8_block":
+            wf = w.w[e].float() * expand_fp8_block_scale(w.scale[e])
         else:
             wf = w.dequantize(e).float()
         wf = wf.t()

@@ -25,7 +25,7 @@ from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 
-from ..config import ModelSpec, resolve_model
+from ..config import ModelSpec, refuse_moe_quantization, resolve_model
 from ..models.llama.model import LlamaBlock
 from ..models.stage import CausalLMStage, apply_quantization, make_block
 
@@ -148,9 +148,13 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
                dtype: torch.dtype = torch.bfloat16, random_init: bool = False,
                seed: int = 0) -> LlamaBlock:
     """Build the block of ``layer_ids`` and load its weights (per layer, only the needed shards).
-    ``use_quantized``: False, True / "fp8", "int8", "mxfp4", "fp8_experts" or "mxfp4_experts"
-    (``apply_quantization``'s modes)."""
+    ``use_quantized``: False, True / "fp8", "int8", "mxfp4", "fp8_experts", "fp8_block_experts"
+    or "mxfp4_experts" (``apply_quantization``'s modes).  A 128 x 128 block-scaled FP8 checkpoint
+    (``quantization_config`` in its config.json) loads its experts as "fp8_block_experts" with no
+    mode given and everything else as bf16; "bf16" dequantises the experts too, and the other
+    quantising modes are refused."""
     spec = _load_config(model_name, cache_dir, token)
+    refuse_moe_quantization(spec, use_quantized)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
     block = make_block(spec, layer_ids, device=device, dtype=dtype)
     if random_init:
@@ -177,6 +181,8 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
     ``quantize="fp8_experts"``: sparse-MoE blocks only — the routed experts' weights as fp8 e4m3
     with one scale per weight row; attention, norms, the router, and in Qwen2-MoE models the dense
     layers and the shared expert, stay bf16.
+    ``quantize="fp8_block_experts"``: the same with one scale per 16 stored weight rows and 128
+    input features (the format of 128 x 128 block-scaled FP8 checkpoints).
     ``quantize="mxfp4_experts"``: the same with MXFP4 expert weights (one e8m0 scale per 32 input
     features of a weight row).
     """

@@ -6,6 +6,8 @@ scripts/bench_mxfp4.py's protocol and helpers.
     python3 scripts/bench_moe.py [--models qwen3-30b-a3b,mixtral-8x7b] [--rows 1,8,64,512] [--out DIR]
     python3 scripts/bench_moe.py --fp8 [...]      fp8 expert weights against bf16 -> moe_fp8.json
     python3 scripts/bench_moe.py --fp4 [...]      MXFP4 and fp8 against bf16 -> moe_fp4.json
+    python3 scripts/bench_moe.py --fp8-block [...]   block-scaled fp8 against per-row fp8 experts
+                                                  -> moe_fp8_block.json
     python3 scripts/bench_moe.py --shared [...]   Qwen2-MoE's shared expert -> moe_shared.json
     python3 scripts/bench_moe.py --tile [...]     the tile GEMM for many rows per expert -> moe_tile.json
     python3 scripts/bench_moe.py --tile --fp8 | --fp4 [...]   the same on quantised experts
@@ -497,6 +499,65 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
     torch.cuda.empty_cache()
 
 
+def bench_fp8_block(torch, ops, F, name, rows, res, a):
+    """Block-scaled fp8 experts (``--fp8-block``) against per-row fp8 experts, the yardstick (the
+    same bytes to within 0.2 %): ``moe_fp8`` / ``moe_fp8_block`` are ops.moe_mlp on
+    ops.quantize_expert_weights_fp8 / _fp8_block of the same bf16 tensors, interleaved in one
+    process.  Few rows run on the weight-streaming kernel, rows from 2048 up on the tile GEMM
+    (``moe_tile_rows_q=32``, set by main)."""
+    from distributed_llm_inference.config import PRESETS
+    spec = PRESETS[name]
+    dev = torch.device("cuda", 0)
+    H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,
+                  spec.num_experts_per_tok)
+    copies = 16 if E * 3 * H * I < (1 << 30) else 3      # bench_model's rule at a byte per weight
+    gen = torch.Generator(device=dev).manual_seed(1)
+    quant = {"fp8": [], "fp8_block": []}
+    for _ in range(copies):
+        wgu = torch.empty(E, 2 * I, H, device=dev, dtype=torch.bfloat16).normal_(
+            0, H ** -0.5, generator=gen)
+        wd = torch.empty(E, H, I, device=dev, dtype=torch.bfloat16).normal_(
+            0, I ** -0.5, generator=gen)
+        for fmt in quant:
+            quant[fmt].append((ops.ExpertWeights.quantize(wgu, fmt),
+                               ops.ExpertWeights.quantize(wd, fmt)))
+        del wgu, wd
+    for T in rows:
+        x = torch.randn(T, H, device=dev, dtype=torch.bfloat16, generator=gen)
+        logits = [torch.randn(T, E, device=dev, generator=gen).to(torch.bfloat16)
+                  for _ in range(copies)]
+        tiles = ops.moe_uses_tiles(T, k, E, "fp8_block", dev)
+        assert tiles == ops.moe_uses_tiles(T, k, E, "fp8", dev)
+        cands = {"moe_" + fmt: (lambda c, q=q: ops.moe_mlp(x, logits[c], q[c][0], q[c][1], k,
+                                                          spec.norm_topk_prob))
+                 for fmt, q in quant.items()}
+        reps = 10 if T <= 2048 else 3
+        graphs = {n: bm._graph(torch, [(lambda c=c, f=f: f(c)) for c in range(copies)])
+                  for n, f in cands.items()}
+        samples = {n: [] for n in cands}
+        for _ in range(7):                            # interleaved: same box, same minute
+            for n in cands:
+                samples[n].append(bm._timed(torch, graphs[n], reps) / copies)
+        row = {"T": T, "copies": copies, "kernel": "tile" if tiles else "weight-streaming"}
+        for n in cands:
+            row[n] = {"us": round(statistics.median(samples[n]), 2),
+                      "min_us": round(min(samples[n]), 2), "max_us": round(max(samples[n]), 2)}
+        a8, ab = row["moe_fp8"], row["moe_fp8_block"]
+        ab["vs_fp8"] = round(ab["us"] / a8["us"], 3)
+        # the ratio's run-to-run range: the extremes of the per-round ratios
+        per_round = [b / f for b, f in zip(samples["moe_fp8_block"], samples["moe_fp8"])]
+        ab["vs_fp8_range"] = [round(min(per_round), 3), round(max(per_round), 3)]
+        ab["separated"] = ab["min_us"] > a8["max_us"] or ab["max_us"] < a8["min_us"]
+        res["models"].setdefault(name, {"H": H, "I": I, "E": E, "k": k, "rows": {}})
+        res["models"][name]["rows"][str(T)] = row
+        print(f"{name:14s} T={T:5d} {row['kernel']:16s} fp8 {a8['us']:9.1f} us  fp8_block "
+              f"{ab['us']:9.1f} us  x{ab['vs_fp8']:.3f} ({ab['vs_fp8_range'][0]:.3f}-"
+              f"{ab['vs_fp8_range'][1]:.3f})", flush=True)
+        bm._save(a, "moe_fp8_block.json", res)
+        del graphs
+        torch.cuda.empty_cache()
+
+
 def bench_shared(torch, ops, F, name, rows, res, a):
     """The Qwen2-MoE block with its shared expert, fused against unfused (module docstring)."""
     from distributed_llm_inference.config import PRESETS
@@ -589,6 +650,9 @@ def main():
     ap.add_argument("--tile", action="store_true",
                     help="the tile GEMM for many rows per expert against the weight-streaming "
                          "kernel and the loop (moe_tile.json)")
+    ap.add_argument("--fp8-block", action="store_true",
+                    help="block-scaled fp8 experts against per-row fp8 experts, streaming kernel "
+                         "and tile GEMM (moe_fp8_block.json)")
     ap.add_argument("--note", default="", help="free text kept in the result file (--fp8 / --fp4)")
     a = ap.parse_args()
     if a.shared and (a.fp8 or a.fp4):
@@ -597,10 +661,12 @@ def main():
         ap.error("--tile measures one quantised format per run: --fp8 or --fp4")
     if a.shared and a.tile:
         ap.error("--shared or --tile, not both")
+    if a.fp8_block and (a.shared or a.tile or a.fp8 or a.fp4):
+        ap.error("--fp8-block is a mode of its own")
     a.models = a.models or ("qwen1.5-moe-a2.7b,qwen2-57b-a14b" if a.shared
                             else "qwen3-30b-a3b,mixtral-8x7b")
     tile_q = a.tile and (a.fp8 or a.fp4)
-    a.rows = a.rows or ("1,4,32,512" if a.shared else "128,512,2048,8192" if tile_q
+    a.rows = a.rows or ("1,8,32,2048,8192" if a.fp8_block else "1,4,32,512" if a.shared else "128,512,2048,8192" if tile_q
                         else "64,512,2048,8192" if a.tile else "1,8,64,512")
     os.makedirs(a.out, exist_ok=True)
     torch = bm._torch()
@@ -681,10 +747,23 @@ def main():
                     "swiglu, F.linear, index_add_ (fp32); routing on the host, not timed",
             "gate_up / down, gate_up_tile / down_tile, gate_up_tile_bf16 / down_tile_bf16":
                 "the two products alone, on each kernel"}
-    if (a.fp8 or a.fp4 or a.shared or a.tile) and a.note:
+    if a.fp8_block:
+        res["unit"] = ("us per MoE layer (median of 7 interleaved rounds of 10 graph replays, 3 "
+                       "past T = 2048, over `copies` layers); vs_fp8 = time / the per-row fp8 "
+                       "twin's; vs_fp8_range = the extremes of that ratio over the 7 rounds")
+        res["candidates"] = {
+            "moe_fp8": "ops.moe_mlp on ops.quantize_expert_weights_fp8 of the bf16 tensors",
+            "moe_fp8_block": "the same on ops.quantize_expert_weights_fp8_block of them; both "
+                             "with moe_tile_rows_q = 32 (row.kernel names the kernel)"}
+    if (a.fp8 or a.fp4 or a.shared or a.tile or a.fp8_block) and a.note:
         res["note"] = a.note
     with torch.no_grad():
         for name in a.models.split(","):
+            if a.fp8_block:
+                with ops.kernel_policy(moe_tile_rows_q=32):
+                    bench_fp8_block(torch, ops, F, name.strip(),
+                                    [int(r) for r in a.rows.split(",")], res, a)
+                continue
             if a.shared:
                 bench_shared(torch, ops, F, name.strip(), [int(r) for r in a.rows.split(",")],
                              res, a)
