@@ -772,6 +772,15 @@ class KernelPolicy:
     # block-scaled tile GEMM, fp8 experts").  bf16 and MXFP4 experts ignore it, and so does every
     # call that moe_tile_rows_q leaves on the weight-streaming kernel
     moe_tile_f8: bool = False
+    # sparse MoE, block-scaled fp8 experts ("fp8_block"): where moe_tile_rows_q sends them to the
+    # tiles, run both products on the block-scaled MFMA with both operands fp8
+    # (csrc/kernels/moe_tile_f8_block.hip; x and h quantised to MX fp8 with row-major scales
+    # first, the weight's fp32 block scale folded in per k-step) instead of widening the weight to
+    # bf16.  Experimental and off: it changes the numerics of those products (fp8 activation
+    # rounding; docs/kernels.md "Sparse MoE: block-scaled tile GEMM, block-scaled fp8 experts").
+    # Every other expert format ignores it, and so does every call that moe_tile_rows_q leaves on
+    # the weight-streaming kernel
+    moe_tile_f8_block: bool = False
 
     _FP8_SHAPES = ("qkv", "o", "gate_up", "down")
 

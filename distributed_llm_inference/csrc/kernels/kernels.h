@@ -261,6 +261,18 @@ int launch_moe_tile_gemm_mx(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, 
                             const int* sorted_pairs, const int* expert_count,
                             const int* expert_offset, int T, int E, int k, int N, int K,
                             int epilogue, hipStream_t stream);
+// The same two products for block-scaled fp8 experts on the block-scaled MFMA with both operands
+// fp8 (moe_tile_f8_block.hip): the stored e4m3 weight bytes times MX fp8 activations (a_q / a_sc
+// as above, gathered the same way), the activation scales on the MFMA's scale operand.  Every
+// MFMA covers one 128-k block of one 16-row group and starts from zero; its result times the
+// block's fp32 scale W.scale [E, N / 16, K / 128] is added to the fp32 accumulator, so nothing
+// is left to scale in the epilogue.  W.format must be kExpertFp8Block (else -6); N % 128 == 0,
+// K % 128 == 0, K <= moe_tile_f8_block_max_k() (else -2); grid and other codes as above
+int moe_tile_f8_block_max_k();
+int launch_moe_tile_gemm_f8_block(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
+                                  const int* sorted_pairs, const int* expert_count,
+                                  const int* expert_offset, int T, int E, int k, int N, int K,
+                                  int epilogue, hipStream_t stream);
 // The same two products for fp8 experts on the block-scaled MFMA with both operands fp8
 // (moe_tile_f8.hip): the stored e4m3 weight bytes times MX fp8 activations (a_q / a_sc as above,
 // gathered the same way), the activation scales on the MFMA's scale operand, the fp32 row scale

@@ -1483,6 +1483,7 @@ MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
 MOE_MAX_TOPK = ref.MOE_MAX_TOPK
 MOE_TILE_MX_MAX_K = 16384  # moe_tile_mx.hip kMaxKt * 128: the activation scales' LDS slot
 MOE_TILE_F8_MAX_K = 16384  # moe_tile_f8.hip kMaxKt * 128: the same slot
+MOE_TILE_F8_BLOCK_MAX_K = 16384  # moe_tile_f8_block.hip kMaxKt * 128: the same slot
 moe_tile_capacity = ref.moe_tile_capacity
 
 
@@ -1572,12 +1573,21 @@ def moe_uses_f8(T: int, k: int, E: int, weight_format: str, device) -> bool:
                 and moe_uses_tiles(T, k, E, weight_format, device))
 
 
+def moe_uses_f8_block(T: int, k: int, E: int, weight_format: str, device) -> bool:
+    """Whether that call runs on the fp8 x fp8 tile GEMM of block-scaled fp8 experts
+    (moe_tile_f8_block.hip, MX fp8 activations): it goes to the tiles (:func:`moe_uses_tiles`),
+    ``KernelPolicy.moe_tile_f8_block`` is set and the experts are ``"fp8_block"``."""
+    return bool(weight_format == "fp8_block" and policy().moe_tile_f8_block
+                and moe_uses_tiles(T, k, E, weight_format, device))
+
+
 def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
                      out: Optional[torch.Tensor] = None,
                      w_scale: Optional[torch.Tensor] = None,
                      w_block_scale: Optional[torch.Tensor] = None,
                      tiles: Optional[bool] = None,
-                     mx: Optional[bool] = None) -> torch.Tensor:
+                     mx: Optional[bool] = None,
+                     f8_block: Optional[bool] = None) -> torch.Tensor:
     """The routed experts' products on the grouped weight-streaming MFMA GEMM (moe.hip), rows in
     ``r.sorted_pairs`` order.  ``down=False``: ``x [T, H]``, ``w [E, 2I, H]`` with every expert's
     rows in :func:`swiglu_interleave` order; returns ``h [P, I] = silu(gate) * up`` of token
@@ -1615,10 +1625,22 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     CPU.  None lets :func:`moe_uses_mx` (``KernelPolicy.moe_tile_mx``) and :func:`moe_uses_f8`
     (``KernelPolicy.moe_tile_f8``) decide, both off by default; False never uses those kernels.
     Block-scaled fp8 experts never run there (an arbitrary fp32 block scale cannot ride on the
-    MFMA's e8m0 scale operand): with ``moe_tile_f8`` set they run on the widening tile GEMM, and
-    ``mx=True`` on them is a ``ValueError``."""
-    if isinstance(x, MxFp8Rows) and mx is not True:
-        raise ValueError("moe_grouped_gemm: MxFp8Rows activations go with mx=True")
+    MFMA's e8m0 scale operand): ``moe_tile_f8`` leaves them where they are, ``mx=True`` on them
+    is a ``ValueError``, and their fp8 x fp8 kernel has a switch of its own.
+
+    ``f8_block`` (block-scaled fp8 experts): True quantises the activations the same way (or takes
+    an :class:`MxFp8Rows`) and multiplies them with the stored e4m3 bytes on the block-scaled MFMA
+    (moe_tile_f8_block.hip).  One instruction covers one 128-k block of one 16-row group, so each
+    starts from zero and its result times the block's fp32 scale is added to the fp32 sum: the
+    numerics of ``dequantize(mx_quantize(x))`` times the dequantised weights in fp32 with the same
+    epilogue rounding, which is what ``f8_block=True`` computes on the CPU.  N % 128 == 0,
+    K % 128 == 0, K <= 16384, ``KernelPolicy.moe_tile_rows_q`` set, neither ``tiles=False`` nor
+    ``mx=True``; anything else, and any other expert format, is a ``ValueError``, never another
+    kernel.  None lets :func:`moe_uses_f8_block` (``KernelPolicy.moe_tile_f8_block``, off by
+    default) decide; False never uses that kernel."""
+    if isinstance(x, MxFp8Rows) and mx is not True and f8_block is not True:
+        raise ValueError("moe_grouped_gemm: MxFp8Rows activations go with mx=True or "
+                         "f8_block=True")
     if isinstance(w, ExpertWeights):
         if w_scale is not None or w_block_scale is not None:
             raise ValueError("moe_grouped_gemm: ExpertWeights carry their scale; w_scale / "
@@ -1649,6 +1671,34 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     dev = x.q.device if isinstance(x, MxFp8Rows) else x.device
     if out is None:
         out = torch.empty(P, N if down else N // 2, dtype=torch.bfloat16, device=dev)
+    if f8_block is None:
+        f8_block = (tiles is not False and not mx
+                    and moe_uses_f8_block(T, k, e.E, e.format, dev))
+    if f8_block:
+        if tiles is False or mx:
+            raise ValueError("moe_grouped_gemm: f8_block=True runs on the tiles, on its own "
+                             "kernel; tiles=False and mx=True exclude it")
+        if e.format != "fp8_block":
+            raise ValueError(f"moe_grouped_gemm: f8_block=True needs block-scaled fp8 expert "
+                             f"weights, got {e.format} (per-row fp8 and MXFP4 experts take "
+                             f"mx=True, bf16 experts keep bf16 activations)")
+        if (w.dtype != FP8 or scale.dtype != torch.float32 or scale.device != w.device
+                or N % 128 or e.K % 128 or e.K > MOE_TILE_F8_BLOCK_MAX_K
+                or tuple(scale.shape) != (w.shape[0], N // 16, e.K // 128)):
+            raise ValueError(f"moe_grouped_gemm: f8_block=True needs e4m3fn weights with fp32 "
+                             f"scales [E, N / 16, K / 128] on their device, N % 128 == 0 and "
+                             f"K % 128 == 0, K <= {MOE_TILE_F8_BLOCK_MAX_K}; got N={N}, K={e.K}")
+        a = x if isinstance(x, MxFp8Rows) else quant_mx_rows(x)
+        if dev.type != "cuda":
+            return ref.moe_grouped_gemm(a.dequantize(), e, r, 1 if down else 0, out)
+        if not policy().moe_tile_rows_q:
+            raise ValueError("moe_grouped_gemm: f8_block=True needs KernelPolicy.moe_tile_rows_q "
+                             "set (with it at 0 quantised experts run on the weight-streaming "
+                             "kernel)")
+        native().moe_tile_gemm_f8_block(out, a.q.contiguous(), a.sc.contiguous(), w,
+                                        r.sorted_pairs, r.expert_count, r.expert_offset, T, k,
+                                        1 if down else 0, scale.contiguous())
+        return out
     if mx is None:
         mx = tiles is not False and (moe_uses_mx(T, k, e.E, e.format, dev)
                                      or moe_uses_f8(T, k, e.E, e.format, dev))
