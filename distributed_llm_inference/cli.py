@@ -40,6 +40,11 @@ def _common(ap: argparse.ArgumentParser) -> None:
     wq.add_argument("--fp4", action="store_true",
                     help="MXFP4 weights (4-bit e2m1 + e8m0 scale per 32: 17/32 byte per "
                          "parameter; the interactive-decode and KV-capacity mode)")
+    wq.add_argument("--fp8-block", action="store_true",
+                    help="block-scaled fp8-e4m3 weights (one fp32 scale per 16 weight rows and 128 "
+                         "input features: 1 + 4/2048 byte per parameter) for every decoder-layer "
+                         "linear and the routed experts; a 128x128 block-scaled FP8 checkpoint "
+                         "runs on its stored bytes")
     wq.add_argument("--fp8-experts", action="store_true",
                     help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
                          "attention, norms, the router, dense layers and a shared expert stay bf16")
@@ -83,6 +88,7 @@ def engine_config(a):
         os.environ["DLI_TRANSPORT"] = a.transport   # read by every rank's make_transport
     quantize = ("fp8" if a.fp8 else "int8" if a.int8
                 else "mxfp4" if getattr(a, "fp4", False)
+                else "fp8_block" if getattr(a, "fp8_block", False)
                 else "fp8_experts" if getattr(a, "fp8_experts", False)
                 else "fp8_block_experts" if getattr(a, "fp8_block_experts", False)
                 else "mxfp4_experts" if getattr(a, "fp4_experts", False) else False)
@@ -120,7 +126,9 @@ def cmd_plan(a) -> int:
     ranges = plan_stages(spec, layout.pp, head_rotation=rotate)
     # bytes per layer parameter: MXFP4 = a nibble + one scale byte per 32 (the norm weights, a
     # few thousand bf16 values per layer, are not told apart)
-    per_param = 17 / 32 if a.fp4 else (1 if (a.fp8 or a.int8) else 2)
+    # block-scaled fp8: a byte + one fp32 scale per 16 rows x 128 k
+    per_param = (17 / 32 if a.fp4 else 1 + 4 / 2048 if getattr(a, "fp8_block", False)
+                 else (1 if (a.fp8 or a.int8) else 2))
     per_layer = int(spec.layer_param_count() * per_param)
     if getattr(a, "fp8_experts", False):
         # experts: a byte per parameter and an fp32 scale per weight row (2 I gate|up rows and H
@@ -133,7 +141,8 @@ def cmd_plan(a) -> int:
         per_param = per_layer / spec.layer_param_count()
     block_fp8 = getattr(a, "fp8_block_experts", False) or (
         spec.weight_quant == "fp8_block" and spec.num_experts
-        and not (a.fp8 or a.int8 or a.fp4 or a.fp8_experts or a.fp4_experts))
+        and not (a.fp8 or a.int8 or a.fp4 or a.fp8_experts or a.fp4_experts
+                 or getattr(a, "fp8_block", False)))
     if block_fp8:
         # experts: a byte per parameter and an fp32 scale per 16 stored rows and 128 k (a 128 x
         # 128 FP8 checkpoint's tables expanded 8x along the rows); the rest of the layer stays bf16

@@ -530,18 +530,20 @@ def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
     and 128 k), or MXFP4 ones under "mxfp4_experts", which leave everything but the experts bf16
     -- and which a model without experts cannot take.  A block-scaled FP8 checkpoint
     (``spec.weight_quant``) holds its experts in the "fp8_block_experts" format already: that mode
-    is its default, "bf16" dequantises everything, and the other quantising modes are refused."""
+    is its default, "bf16" dequantises everything, and the other quantising modes are refused.
+    "fp8_block" (block-scaled fp8 for every decoder-layer linear and the routed experts) is
+    admitted for dense and sparse models, FP8 checkpoints included."""
     if mode in ("fp8_experts", "mxfp4_experts", "fp8_block_experts") and not spec.num_experts:
         raise ValueError(f"{mode} needs a sparse MoE model; {spec.name} ({spec.model_type}) "
                          "has no experts")
     if spec.weight_quant and spec.num_experts and mode not in (False, None, "none", "bf16",
-                                                               "fp8_block_experts"):
+                                                               "fp8_block_experts", "fp8_block"):
         mode = "fp8" if mode is True else mode
         raise ValueError(f"{mode}: {spec.name} is a block-scaled FP8 checkpoint, whose experts "
                          "load as fp8_block_experts (the default; \"bf16\" dequantises them); "
                          "requantising them to another format is not supported")
     if spec.num_experts and mode not in (False, None, "none", "bf16", "fp8_experts",
-                                         "mxfp4_experts", "fp8_block_experts"):
+                                         "mxfp4_experts", "fp8_block_experts", "fp8_block"):
         mode = "fp8" if mode is True else mode
         raise ValueError(f"{mode} weights are not supported for sparse MoE layers "
                          f"({spec.model_type}, {spec.name}): the grouped expert GEMM takes bf16 "

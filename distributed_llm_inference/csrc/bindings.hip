@@ -1087,6 +1087,45 @@ void small_gemm_fp8(Tensor out, Tensor x, Tensor w, Tensor wscale, optional<Tens
            "small_gemm_fp8");
 }
 
+// dense block-scaled fp8: e4m3 weights [N, K] + fp32 scales [N / 16, K / 128], bf16 rows.  1-32
+// rows: gemm_fp8_block_small.hip; more: gemm_fp8_block_tile.hip
+void linear_fp8_block(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Tensor> bias,
+                      bool swiglu) {
+  CHECK_IN(out); CHECK_IN(x); CHECK_IN(w); CHECK_IN(bscale);
+  CHECK_BF16(out); CHECK_BF16(x); CHECK_F32(bscale);
+  TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, "linear_fp8_block: fp8 e4m3fn weights");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && w.dim() == 2 && bscale.dim() == 2,
+              "linear_fp8_block: 2-D tensors");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M >= 1 && M <= (1 << 24), "linear_fp8_block: M in [1, 2^24]");
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "linear_fp8_block: needs K % 128 == 0");
+  TORCH_CHECK(N >= 128 && N % 128 == 0 && N <= (1 << 24), "linear_fp8_block: needs N % 128 == 0");
+  TORCH_CHECK(w.size(1) == K && bscale.size(0) == N / 16 && bscale.size(1) == K / 128,
+              "linear_fp8_block: weight [N, K], scales [N / 16, K / 128]");
+  TORCH_CHECK(!swiglu || !bias.has_value(), "linear_fp8_block: swiglu takes no bias");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == (swiglu ? N / 2 : N),
+              "linear_fp8_block: shape mismatch");
+  TORCH_CHECK(out.device() == x.device() && w.device() == x.device() &&
+                  bscale.device() == x.device(), "linear_fp8_block: one device");
+  const dli::bf16* b = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N && bias->device() == x.device(),
+                "linear_fp8_block: bias must have N entries");
+    b = bp(*bias);
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  const uint8_t* wp = static_cast<const uint8_t*>(w.data_ptr());
+  if (M <= 32)
+    check_rc(dli::launch_small_gemm_fp8_block(bp(out), bp(x), wp, bscale.data_ptr<float>(), b,
+                                              (int)M, (int)N, (int)K, swiglu, cur_stream()),
+             "linear_fp8_block (small)");
+  else
+    check_rc(dli::launch_gemm_fp8_block_tile(bp(out), bp(x), wp, bscale.data_ptr<float>(), b,
+                                             (int)M, (int)N, (int)K, swiglu, cur_stream()),
+             "linear_fp8_block (tile)");
+}
+
 // ------------------------------------------------------------------------------ sparse MoE (moe.hip)
 // num_experts (with shared_w): logits [T, ld], ld > num_experts, column num_experts the shared
 // expert's gate logit; shared_w [T] gets its sigmoid
@@ -1703,6 +1742,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("small_gemm_fp8", &small_gemm_fp8,
         "y = (x . W8^T) * w_scale (+ bias), fp8 weights, 3-32 bf16 rows (weight-streaming MFMA GEMM)",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("w_scale"),
+        py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("linear_fp8_block", &linear_fp8_block,
+        "y = x . (W8 (.) block_scale)^T (+ bias), block-scaled fp8 weights (16 x 128 fp32 scales), "
+        "bf16 rows: weight-streaming MFMA GEMM at 1-32 rows, LDS-staged MFMA tile GEMM beyond",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("moe_topk", &moe_topk, "router logits [T, E] -> top-k expert ids + bf16-rounded weights",
         py::arg("ids"), py::arg("w"), py::arg("logits"), py::arg("renorm"),

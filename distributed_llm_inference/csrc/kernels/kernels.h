@@ -194,6 +194,18 @@ int launch_small_gemm_fp4(bf16* y, const bf16* x, const uint8_t* W, const uint8_
 int launch_small_gemm_fp8(bf16* y, const bf16* x, const uint8_t* W, const float* wscale,
                           const bf16* bias, int M, int N, int K, bool swiglu,
                           hipStream_t stream);
+// Dense block-scaled fp8 weights (W8 [N, K] e4m3fn bytes, bscale [N / 16, K / 128] fp32: one
+// factor per 16 weight rows and 128 k) x bf16 rows, the scale applied inside the k-loop:
+// y[M, N] = x . (W8 (.) bscale)^T (+ bias); N % 128 == 0, K % 128 == 0.  swiglu: W8 is
+// swiglu_interleave'd gate|up (no bias), y is silu(gate) * up [M, N / 2].
+// 1 <= M <= 32: weight-streaming on the bf16 MFMA (gemm_fp8_block_small.hip)
+int launch_small_gemm_fp8_block(bf16* y, const bf16* x, const uint8_t* W, const float* bscale,
+                                const bf16* bias, int M, int N, int K, bool swiglu,
+                                hipStream_t stream);
+// any M >= 1, meant for M > 32: LDS-staged 128 x 128 MFMA tiles (gemm_fp8_block_tile.hip)
+int launch_gemm_fp8_block_tile(bf16* y, const bf16* x, const uint8_t* W, const float* bscale,
+                               const bf16* bias, int M, int N, int K, bool swiglu,
+                               hipStream_t stream);
 // Sparse MoE MLP on bf16 expert weights (moe.hip).  P = T k (token, slot) pairs; E <= 256, k <= 8.
 // Every grid depends on (T, E, k, N) only and every count is read from device memory.
 // tile table capacity: min(E, P) + P / 32

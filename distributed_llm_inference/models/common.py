@@ -70,7 +70,8 @@ MXFP4_SCRATCH = _Mxfp4Scratch()
 
 
 class Linear(nn.Module):
-    """``y = x W^T (+ b)`` with W stored [out, in]; optional fp8 / LLM.int8 / MXFP4 weights."""
+    """``y = x W^T (+ b)`` with W stored [out, in]; optional fp8 / LLM.int8 / MXFP4 / block-scaled fp8
+    weights."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False,
                  dtype: torch.dtype = torch.bfloat16, device=None):
@@ -87,6 +88,9 @@ class Linear(nn.Module):
         # MXFP4: e2m1 nibbles [out, in / 2] + e8m0 block exponents [out, in / 32]
         self.register_buffer("weight_fp4", None, persistent=False)
         self.register_buffer("weight_block_scale", None, persistent=False)
+        # block-scaled fp8: e4m3fn bytes [out, in] + fp32 scales [out / 16, in / 128]
+        self.register_buffer("weight_fp8_block", None, persistent=False)
+        self.register_buffer("weight_fp8_block_scale", None, persistent=False)
         self.int8_threshold = 0.0
         # which projection of its layer this is ("qkv" / "o" / "gate_up" / "down", set by the
         # model): KernelPolicy.fp8_gemm4 routes fp8 products per role
@@ -103,6 +107,54 @@ class Linear(nn.Module):
     @property
     def is_fp4(self) -> bool:
         return self.weight_fp4 is not None
+
+    @property
+    def is_fp8_block(self) -> bool:
+        """Block-scaled fp8 weights (one fp32 scale per 16 rows x 128 input features).  Not
+        :attr:`is_fp8`: none of the per-row fp8 paths (quantised rows, deferred reductions, the
+        GEMV and its fused prologues) knows this format; every product is
+        :func:`ops.linear_fp8_block` on bf16 rows."""
+        return self.weight_fp8_block is not None
+
+    @staticmethod
+    def fp8_block_shape_ok(out_features: int, in_features: int) -> bool:
+        """The shapes the block-scaled fp8 kernels take: both sides whole 128 x 128 blocks."""
+        return out_features % 128 == 0 and in_features % 128 == 0
+
+    def quantize_fp8_block(self, keep_bf16: bool = False) -> bool:
+        """Quantise W to block-scaled fp8 with the arithmetic of
+        :func:`ops.quantize_expert_weights_fp8_block` (E = 1): e4m3fn bytes and one fp32 scale
+        ``amax / 448`` per 16 rows and 128 input features.  Needs ``in_features % 128 == 0`` and
+        ``out_features % 128 == 0``; a Linear of any other shape is left as it is -- bf16 for
+        good, decided here once and never per call -- and False is returned.  Frees the bf16 copy
+        unless asked not to.  Bias stays bf16."""
+        if not self.fp8_block_shape_ok(self.out_features, self.in_features):
+            return False
+        w8, scale = ops.quantize_expert_weights_fp8_block(self.weight.data[None])
+        self.adopt_fp8_block(w8[0], scale[0], keep_bf16=keep_bf16)
+        return True
+
+    def adopt_fp8_block(self, w8: torch.Tensor, scale: torch.Tensor,
+                        keep_bf16: bool = False) -> None:
+        """Take stored e4m3fn bytes ``[out, in]`` and fp32 scales ``[out / 16, in / 128]`` as this
+        Linear's weight (a checkpoint's bytes with its 128-row scales repeated over their eight
+        16-row groups).  No arithmetic touches the bytes."""
+        N, K = self.out_features, self.in_features
+        if not self.fp8_block_shape_ok(N, K):
+            raise ValueError(f"block-scaled fp8 needs out % 128 == 0 and in % 128 == 0, got "
+                             f"[{N}, {K}]")
+        if w8.dtype != ops.FP8 or tuple(w8.shape) != (N, K):
+            raise ValueError(f"adopt_fp8_block: e4m3fn bytes [{N}, {K}], got {w8.dtype} "
+                             f"{tuple(w8.shape)}")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (N // 16, K // 128):
+            raise ValueError(f"adopt_fp8_block: fp32 scales [{N // 16}, {K // 128}], got "
+                             f"{scale.dtype} {tuple(scale.shape)}")
+        dev = self.weight.device
+        self.weight_fp8_block = w8.to(dev).contiguous()
+        self.weight_fp8_block_scale = scale.to(dev).contiguous()
+        if not keep_bf16:
+            self.weight = nn.Parameter(torch.empty(0, dtype=self.weight.dtype, device=dev),
+                                       requires_grad=False)
 
     def quantize_mxfp4(self, keep_bf16: bool = False) -> None:
         """Quantise W to MXFP4 (OCP MX: 4-bit e2m1 elements, one e8m0 scale per 32 input
@@ -170,7 +222,7 @@ class Linear(nn.Module):
         """Split-K factor if ``gemm_tile`` takes this product on the GPU, else 0."""
         if (self.bias is not None or not x.is_cuda or x.dim() != 2 or x.dtype != torch.bfloat16
                 or not x.is_contiguous() or self.weight_fp8 is not None
-                or self.weight_int8 is not None):
+                or self.weight_int8 is not None or self.weight_fp8_block is not None):
             return 0
         return ops.tile_gemm_splits(x.shape[0], self.out_features, self.in_features)
 
@@ -219,8 +271,8 @@ class Linear(nn.Module):
     def gemv_ok(self, rows: int, swiglu: bool = False, bf16_rows: bool = True) -> bool:
         """Whether :meth:`gemv` takes a product of ``rows`` GPU rows (bf16 rows, or with
         ``bf16_rows=False`` the fused quantiser's fp8 rows for fp8 weights)."""
-        if not 1 <= rows <= ops.SKINNY_DISPATCH_M:
-            return False
+        if not 1 <= rows <= ops.SKINNY_DISPATCH_M or self.weight_fp8_block is not None:
+            return False   # block-scaled fp8: ops.linear_fp8_block takes 1-2 rows as well
         if swiglu and (self.bias is not None or self.out_features % 32):
             return False
         if self.weight_fp4 is not None:
@@ -300,6 +352,13 @@ class Linear(nn.Module):
         """``x_q`` = (fp8 rows, scales) already quantised by a fused producer kernel; then ``x`` may
         be None (fp8 weights only).  ``defer_reduce``: a split-K tile GEMM returns its fp32
         partials (``ops.SplitKPartials``) for an RMSNorm consumer to reduce."""
+        if self.weight_fp8_block is not None:
+            # block-scaled fp8: the stored bytes on bf16 rows, the scale inside the k-loop
+            # (csrc/kernels/gemm_fp8_block_small.hip at 1-32 rows, gemm_fp8_block_tile.hip
+            # beyond); a plain bf16 tensor, nothing deferred
+            y = ops.linear_fp8_block(x.reshape(-1, self.in_features), self.weight_fp8_block,
+                                     self.weight_fp8_block_scale, self.bias)
+            return y.reshape(*x.shape[:-1], self.out_features)
         if self.weight_int8 is not None:
             if (x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= ops.SKINNY_DISPATCH_M
                     and x.dtype == torch.bfloat16 and self.in_features % 16 == 0
@@ -393,7 +452,8 @@ class Linear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in={self.in_features}, out={self.out_features}, bias={self.bias is not None}, "
-                f"fp8={self.is_fp8}, int8={self.is_int8}, fp4={self.is_fp4}")
+                f"fp8={self.is_fp8}, int8={self.is_int8}, fp4={self.is_fp4}"
+                + (", fp8_block=True" if self.is_fp8_block else ""))
 
 
 @dataclass

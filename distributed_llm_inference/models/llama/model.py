@@ -105,6 +105,31 @@ class LlamaBlock(nn.Module):
                 lin.quantize_mxfp4()
         return self
 
+    def quantize_fp8_block(self) -> "LlamaBlock":
+        """Block-scaled fp8 (e4m3, one fp32 scale per 16 rows and 128 input features) weights for
+        every decoder-layer linear (qkv, o, gate|up, down, a shared expert's) and the routed
+        experts of sparse-MoE layers.  Linears and experts that a 128 x 128 FP8 checkpoint was
+        loaded into under this mode hold their stored bytes already and are left as they are; a
+        linear whose sides are not multiples of 128 stays bf16 (Linear.quantize_fp8_block).
+        Norms and the router stay bf16."""
+        for layer in self.layers:
+            mlps = [layer.mlp.shared_expert] if layer.is_moe and layer.mlp.shared_size else (
+                [] if layer.is_moe else [layer.mlp])
+            for mlp in mlps:
+                fused = mlp.fused_swiglu
+                if not mlp.gate_up_proj.is_fp8_block:   # quantise the stored row order
+                    mlp.set_fused_swiglu(False)
+                for lin in (mlp.gate_up_proj, mlp.down_proj):
+                    if not lin.is_fp8_block:
+                        lin.quantize_fp8_block()
+                mlp.set_fused_swiglu(fused)
+            for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj):
+                if not lin.is_fp8_block:
+                    lin.quantize_fp8_block()
+            if layer.is_moe and not layer.mlp.is_fp8_block:
+                layer.mlp.quantize_experts_fp8_block()
+        return self
+
     def quantize_experts_fp8(self) -> "LlamaBlock":
         """fp8 (e4m3, per-row scales) weights for the routed experts of every sparse-MoE layer;
         attention projections, norms, the router, dense layers and the shared expert stay bf16

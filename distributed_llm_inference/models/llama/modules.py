@@ -186,6 +186,16 @@ class LlamaMLP(nn.Module):
                 # per-row blocks along K: quantisation commutes with the row permutation
                 w.weight_fp4.copy_(perm(w.weight_fp4))
                 w.weight_block_scale.copy_(perm(w.weight_block_scale))
+            elif w.is_fp8_block:
+                # bytes as bytes; 16 stored rows are 16 consecutive rows of one projection in
+                # either order, so scale group j of the new order is group src[16 j] / 16
+                w8, sc = w.weight_fp8_block, w.weight_fp8_block_scale
+                w8.copy_(perm(w8.view(torch.uint8)).view(w8.dtype))
+                grp = ops._swiglu_src(w.out_features, sc.device)[::16] // 16
+                if on:
+                    sc.copy_(sc[grp])
+                else:
+                    sc[grp] = sc.clone()
             elif w.is_fp8:
                 # per-output-channel quantisation commutes with the row permutation
                 w.weight_fp8.copy_(perm(w.weight_fp8.view(torch.uint8)).view(w.weight_fp8.dtype))
@@ -201,6 +211,16 @@ class LlamaMLP(nn.Module):
             h = gp.gemv(normed, swiglu=True, norm=norm)
             if h is None:
                 raise RuntimeError("fused-norm gate|up: the GEMV does not take this product")
+            return self.down_proj(h, defer_reduce=defer_reduce)
+        if gp.is_fp8_block:
+            # block-scaled fp8 gate|up: the stored bytes on bf16 rows at any row count, SwiGLU in
+            # the kernels' epilogue once the rows are interleaved; down_proj dispatches itself
+            if self.fused_swiglu:
+                h = ops.linear_fp8_block(normed.reshape(-1, gp.in_features), gp.weight_fp8_block,
+                                         gp.weight_fp8_block_scale, swiglu=True)
+                h = h.reshape(*normed.shape[:-1], self.intermediate_size)
+            else:
+                h = ops.silu_mul(gp(normed))
             return self.down_proj(h, defer_reduce=defer_reduce)
         if self.fused_swiglu and ops.policy().gemv:
             # 1-2 decode rows: SwiGLU in the weight-streaming GEMV's epilogue (any weight dtype)
@@ -410,7 +430,7 @@ class MoEMLP(nn.Module):
                            shared=shared)
 
     # ------------------------------------------------------------------ weights
-    def load_hf(self, g, sd: dict, dt: torch.dtype) -> None:
+    def load_hf(self, g, sd: dict, dt: torch.dtype, keep_fp8_block: bool = False) -> None:
         """From a layer state dict ``sd`` (``g`` = its checked getter): the hub's per-expert keys
         (Qwen3-MoE ``mlp.experts.{e}.{gate,up,down}_proj.weight``, Mixtral
         ``block_sparse_moe.experts.{e}.{w1,w3,w2}.weight`` with w1 = gate, w3 = up, w2 = down), or
@@ -441,12 +461,15 @@ class MoEMLP(nn.Module):
             self.gate.weight[self.num_experts:].copy_(
                 g(pre + "shared_expert_gate.weight").reshape(1, -1).to(dt))
             sh = self.shared_expert
-            gu = torch.cat([g(pre + "shared_expert.gate_proj.weight"),
-                            g(pre + "shared_expert.up_proj.weight")], 0)
-            if sh.fused_swiglu:
-                gu = ops.swiglu_interleave(gu)
-            sh.gate_up_proj.weight.copy_(gu.to(dt))
-            sh.down_proj.weight.copy_(g(pre + "shared_expert.down_proj.weight").to(dt))
+            sk = [pre + f"shared_expert.{n}_proj.weight" for n in ("gate", "up", "down")]
+            if not (keep_fp8_block and adopt_fp8_block_linear(sh.gate_up_proj, sd, sk[:2],
+                                                              sh.fused_swiglu)):
+                gu = torch.cat([g(sk[0]), g(sk[1])], 0)
+                if sh.fused_swiglu:
+                    gu = ops.swiglu_interleave(gu)
+                sh.gate_up_proj.weight.copy_(gu.to(dt))
+            if not (keep_fp8_block and adopt_fp8_block_linear(sh.down_proj, sd, sk[2:])):
+                sh.down_proj.weight.copy_(g(sk[2]).to(dt))
         if pre + "experts.gate_up_proj" in sd:
             gu, down = g(pre + "experts.gate_up_proj"), g(pre + "experts.down_proj")
             if gu.shape != self.w_gate_up.shape or down.shape != self.w_down.shape:
@@ -548,6 +571,42 @@ def dequantize_fp8_block_weight(name: str, w8: torch.Tensor, scale_inv: torch.Te
     return (w8.float() * s).to(torch.bfloat16)
 
 
+def adopt_fp8_block_linear(lin: Linear, sd: dict, keys, interleave: bool = False) -> bool:
+    """The "fp8_block" mode's load of one Linear from a 128 x 128 block-scaled FP8 checkpoint:
+    the stored e4m3fn bytes of ``keys`` (q|k|v, gate|up, or a single weight), concatenated along
+    the rows, become the Linear's weight as they are, and every projection's ``weight_scale_inv``
+    is repeated over the eight 16-row groups of its 128-row blocks before the concatenation.
+    ``interleave``: rows to ops.swiglu_interleave order (bytes as bytes, 16-row scale groups by
+    ``src[::16] // 16``, as MoEMLP._load_fp8_block does).  Returns False, touching nothing, when
+    the tensors are not block-scaled fp8 or the shapes do not fit the kernels (the Linear's sides
+    not multiples of 128, a projection's rows not a multiple of 16): the caller then loads the
+    weight as bf16 through :func:`dequantize_fp8_block_weight`, once, at load."""
+    f8 = torch.float8_e4m3fn
+    K = lin.in_features
+    if not Linear.fp8_block_shape_ok(lin.out_features, K):
+        return False
+    parts = []
+    for k in keys:
+        w, s = sd.get(k), sd.get(k + "_scale_inv")
+        if w is None or s is None or w.dtype != f8 or w.dim() != 2 or w.shape[1] != K \
+                or w.shape[0] % 16:
+            return False
+        rows = w.shape[0]
+        if tuple(s.shape) != ((rows + 127) // 128, K // 128):
+            raise ValueError(f"{k}_scale_inv: expected [{(rows + 127) // 128}, {K // 128}] for "
+                             f"weight_block_size [128, 128], got {tuple(s.shape)}")
+        parts.append((w, s.float().repeat_interleave(8, 0)[:rows // 16]))
+    w8 = torch.cat([w.view(torch.uint8) for w, _ in parts], 0)
+    scale = torch.cat([s for _, s in parts], 0)
+    if w8.shape[0] != lin.out_features:
+        return False
+    if interleave:
+        src = ops._swiglu_src(lin.out_features, w8.device)
+        w8, scale = w8[src], scale[src[::16] // 16]
+    lin.adopt_fp8_block(w8.contiguous().view(f8), scale.contiguous())
+    return True
+
+
 class LlamaDecoderLayer(nn.Module):
     """One decoder layer; ``layer_idx`` is the GLOBAL layer index (as in the reference)."""
 
@@ -647,9 +706,11 @@ class LlamaDecoderLayer(nn.Module):
         return self.mlp(None, x_q=xq, defer_reduce=defer_out), res_out
 
     # ------------------------------------------------------------------ weights
-    def load_hf_state_dict(self, sd: dict) -> None:
+    def load_hf_state_dict(self, sd: dict, keep_fp8_block: bool = False) -> None:
         """Load a HF ``LlamaDecoderLayer`` state dict (keys relative to ``model.layers.{i}.``),
-        fusing q|k|v and gate|up into the single GEMM weights."""
+        fusing q|k|v and gate|up into the single GEMM weights.  ``keep_fp8_block`` (the
+        "fp8_block" mode): the linears of a 128 x 128 block-scaled FP8 checkpoint keep their
+        stored bytes (:func:`adopt_fp8_block_linear`) instead of becoming bf16."""
         def g(k):
             if k not in sd:
                 raise KeyError(f"parameter {k} not found in state dict for layer {self.layer_idx}")
@@ -658,10 +719,15 @@ class LlamaDecoderLayer(nn.Module):
             return sd[k]
         dt = self.input_layernorm.weight.dtype
         with torch.no_grad():
-            qkv = torch.cat([g("self_attn.q_proj.weight"), g("self_attn.k_proj.weight"),
-                             g("self_attn.v_proj.weight")], 0)
-            self.self_attn.qkv_proj.weight.copy_(qkv.to(dt))
-            self.self_attn.o_proj.weight.copy_(g("self_attn.o_proj.weight").to(dt))
+            def adopt(lin, *keys, interleave=False):
+                return keep_fp8_block and adopt_fp8_block_linear(lin, sd, keys, interleave)
+            if not adopt(self.self_attn.qkv_proj, "self_attn.q_proj.weight",
+                         "self_attn.k_proj.weight", "self_attn.v_proj.weight"):
+                qkv = torch.cat([g("self_attn.q_proj.weight"), g("self_attn.k_proj.weight"),
+                                 g("self_attn.v_proj.weight")], 0)
+                self.self_attn.qkv_proj.weight.copy_(qkv.to(dt))
+            if not adopt(self.self_attn.o_proj, "self_attn.o_proj.weight"):
+                self.self_attn.o_proj.weight.copy_(g("self_attn.o_proj.weight").to(dt))
             if self.self_attn.qkv_proj.bias is not None:   # Llama attention_bias, Qwen2
                 self.self_attn.qkv_proj.bias.copy_(torch.cat(
                     [g("self_attn.q_proj.bias"), g("self_attn.k_proj.bias"),
@@ -672,13 +738,16 @@ class LlamaDecoderLayer(nn.Module):
                 self.self_attn.q_norm.weight.copy_(g("self_attn.q_norm.weight").to(dt))
                 self.self_attn.k_norm.weight.copy_(g("self_attn.k_norm.weight").to(dt))
             if self.is_moe:
-                self.mlp.load_hf(g, sd, dt)
+                self.mlp.load_hf(g, sd, dt, keep_fp8_block=keep_fp8_block)
             else:
-                gu = torch.cat([g("mlp.gate_proj.weight"), g("mlp.up_proj.weight")], 0)
-                if self.mlp.fused_swiglu:
-                    gu = ops.swiglu_interleave(gu)
-                self.mlp.gate_up_proj.weight.copy_(gu.to(dt))
-                self.mlp.down_proj.weight.copy_(g("mlp.down_proj.weight").to(dt))
+                if not adopt(self.mlp.gate_up_proj, "mlp.gate_proj.weight", "mlp.up_proj.weight",
+                             interleave=self.mlp.fused_swiglu):
+                    gu = torch.cat([g("mlp.gate_proj.weight"), g("mlp.up_proj.weight")], 0)
+                    if self.mlp.fused_swiglu:
+                        gu = ops.swiglu_interleave(gu)
+                    self.mlp.gate_up_proj.weight.copy_(gu.to(dt))
+                if not adopt(self.mlp.down_proj, "mlp.down_proj.weight"):
+                    self.mlp.down_proj.weight.copy_(g("mlp.down_proj.weight").to(dt))
                 if self.mlp.gate_up_proj.bias is not None:     # Llama mlp_bias
                     self.mlp.gate_up_proj.bias.copy_(torch.cat(
                         [g("mlp.gate_proj.bias"), g("mlp.up_proj.bias")], 0).to(dt))

@@ -28,7 +28,10 @@ def apply_quantization(block, mode, threshold: float = 6.0):
     "mxfp4_experts" (sparse-MoE models: MXFP4 expert weights, the rest bf16), or
     "fp8_block_experts" (sparse-MoE models: e4m3 expert weights with one scale per 16 stored rows
     and 128 input features -- what a 128 x 128 block-scaled FP8 checkpoint loads as, so there the
-    mode changes nothing; on bf16 experts it quantises them).  "bf16" also dequantises experts
+    mode changes nothing; on bf16 experts it quantises them), or "fp8_block" (that format for
+    every decoder-layer linear -- qkv, o, gate|up, down, a shared expert -- and the routed experts;
+    what a 128 x 128 FP8 checkpoint loaded under this mode holds already is left as it is;
+    embedding, LM head, router and norms stay bf16).  "bf16" also dequantises experts
     that were loaded from such a checkpoint; False / None / "none" leave them as loaded."""
     if mode == "bf16" and hasattr(block, "dequantize_experts"):
         return block.dequantize_experts()
@@ -43,6 +46,11 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise NotImplementedError(f"MXFP4 weights are not implemented for "
                                       f"{type(block).__name__} (Llama-family blocks only)")
         return block.quantize_mxfp4()
+    if mode == "fp8_block":
+        if not hasattr(block, "quantize_fp8_block"):
+            raise NotImplementedError(f"block-scaled fp8 weights are not implemented for "
+                                      f"{type(block).__name__} (Llama-family blocks only)")
+        return block.quantize_fp8_block()
     if mode == "fp8_experts":
         if not hasattr(block, "quantize_experts_fp8"):
             raise ValueError(f"fp8_experts needs a sparse MoE model; {type(block).__name__} has "
@@ -58,7 +66,7 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise ValueError(f"fp8_block_experts needs a sparse MoE model; "
                              f"{type(block).__name__} has no experts")
         return block.quantize_experts_fp8_block()
-    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / "
+    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / fp8_block / "
                      "fp8_experts / fp8_block_experts / mxfp4_experts)")
 
 

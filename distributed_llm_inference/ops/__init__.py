@@ -1418,6 +1418,62 @@ def small_gemm_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor,
     return out
 
 
+FP8_BLOCK_SMALL_MAX_M = 32   # rows of gemm_fp8_block_small.hip; more run gemm_fp8_block_tile.hip
+
+
+def linear_fp8_block(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
+                     bias: Optional[torch.Tensor] = None, swiglu: bool = False,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = x . (w8 (.) scale)^T (+ bias)`` for bf16 rows ``x [M, K]`` and a dense block-scaled
+    fp8 weight: ``w8 [N, K]`` e4m3fn, ``scale [N / 16, K / 128]`` fp32, one factor per 16 weight
+    rows and 128 input features (a 128 x 128 FP8 checkpoint's ``weight_scale_inv`` repeated over
+    its eight 16-row groups; :func:`quantize_expert_weights_fp8_block` with E = 1).
+    N % 128 == 0, K % 128 == 0.  The activations are never quantised; the weight is widened
+    exactly, the block's scale multiplies the block's fp32 sum inside the k-loop, and the result
+    is rounded to bf16 once.  1-32 rows: the weight-streaming MFMA kernel
+    (gemm_fp8_block_small.hip); more: the LDS-staged MFMA tile GEMM (gemm_fp8_block_tile.hip).
+    ``swiglu``: the weight is a swiglu_interleave'd gate|up weight (no bias), returns
+    silu(gate) * up ``[M, N / 2]``.  CPU: the torch oracle (fp32 ``w8.float() * expanded scale``,
+    fp32 product, one rounding)."""
+    name = "linear_fp8_block"
+    if x.dim() != 2 or w8.dim() != 2 or scale.dim() != 2:
+        raise ValueError(f"{name}: x [M, K], w8 [N, K] and scale [N / 16, K / 128] are 2-D, got "
+                         f"x {tuple(x.shape)}, w8 {tuple(w8.shape)}, scale {tuple(scale.shape)}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: x must be bfloat16, got {x.dtype}")
+    if w8.dtype != FP8:
+        raise ValueError(f"{name}: w8 must be float8_e4m3fn, got {w8.dtype}")
+    if scale.dtype != torch.float32:
+        raise ValueError(f"{name}: scale must be float32, got {scale.dtype}")
+    M, K = x.shape
+    N = w8.shape[0]
+    if M < 1:
+        raise ValueError(f"{name}: x needs at least one row")
+    if K % ref.FP8_BLOCK_K or w8.shape[1] != K:
+        raise ValueError(f"{name}: K % 128 == 0 and w8 [N, K] must match x [M, K], got "
+                         f"x {tuple(x.shape)}, w8 {tuple(w8.shape)}")
+    if N == 0 or N % 128:
+        raise ValueError(f"{name}: N % 128 == 0, got w8 {tuple(w8.shape)}")
+    if tuple(scale.shape) != (N // ref.FP8_BLOCK_ROWS, K // ref.FP8_BLOCK_K):
+        raise ValueError(f"{name}: scale must be [N / 16, K / 128] = "
+                         f"[{N // ref.FP8_BLOCK_ROWS}, {K // ref.FP8_BLOCK_K}], got "
+                         f"{tuple(scale.shape)}")
+    if bias is not None and (swiglu or bias.dtype != torch.bfloat16 or bias.numel() != N):
+        raise ValueError(f"{name}: bias must be {N} bfloat16 values and is not taken with swiglu")
+    if not (w8.is_contiguous() and scale.is_contiguous()):
+        raise ValueError(f"{name}: w8 and scale must be contiguous")
+    if not _gpu(x):
+        y = x.float() @ (w8.float() * ref.expand_fp8_block_scale(scale)).t()
+        if bias is not None:
+            y = y + bias.float()
+        y = _swiglu_ref(y) if swiglu else y.to(torch.bfloat16)
+        return out.copy_(y) if out is not None else y
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=x.device)
+    native().linear_fp8_block(out, x.contiguous(), w8, scale, bias, swiglu)
+    return out
+
+
 def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor],
                          bias: Optional[torch.Tensor], positions: Optional[torch.Tensor],
                          slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],

@@ -46,7 +46,9 @@ class EngineConfig:
                                     # "mxfp4" / "fp4" (4-bit MX weights) | "fp8_experts" (sparse
                                     # MoE: e4m3 expert weights, the rest bf16) |
                                     # "fp8_block_experts" (the same, block scales) | "mxfp4_experts"
-                                    # (sparse MoE: MXFP4 expert weights, the rest bf16)
+                                    # (sparse MoE: MXFP4 expert weights, the rest bf16) |
+                                    # "fp8_block" (block-scaled e4m3 for every decoder-layer
+                                    # linear and the routed experts; an FP8 checkpoint as stored)
     int8_threshold: float = 6.0     # LLM.int8 outlier threshold (quantize="int8")
     pp: int = 1
     dp: int = 1                     # pipeline replicas (world = dp x pp in init_pipeline_rank)

@@ -152,7 +152,9 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
     or "mxfp4_experts" (``apply_quantization``'s modes).  A 128 x 128 block-scaled FP8 checkpoint
     (``quantization_config`` in its config.json) loads its experts as "fp8_block_experts" with no
     mode given and everything else as bf16; "bf16" dequantises the experts too, and the other
-    quantising modes are refused."""
+    quantising modes are refused -- but "fp8_block", under which every decoder-layer linear of
+    such a checkpoint keeps its stored bytes as well (on a bf16 checkpoint or random init the mode
+    quantises them)."""
     spec = _load_config(model_name, cache_dir, token)
     refuse_moe_quantization(spec, use_quantized)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
@@ -164,7 +166,10 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
         for layer in block.layers:
             log.info("loading weights for layer %d", layer.layer_idx)
             sd = get_block_state_dict(model_name, layer.layer_idx, cache_dir, token, prefix_fmt)
-            layer.load_hf_state_dict(sd)
+            if use_quantized == "fp8_block" and spec.arch == "llama":
+                layer.load_hf_state_dict(sd, keep_fp8_block=True)   # the stored bytes stay
+            else:
+                layer.load_hf_state_dict(sd)
     apply_quantization(block, use_quantized)
     return block
 
@@ -198,8 +203,11 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
 
 
 # --------------------------------------------------------------------------- whole stages
-def load_stage_weights(stage: CausalLMStage, model_name: str, cache_dir=None, token=False) -> None:
-    """Load layers + (embedding / final norm / LM head, if owned) of a stage from a checkpoint."""
+def load_stage_weights(stage: CausalLMStage, model_name: str, cache_dir=None, token=False,
+                       keep_fp8_block: bool = False) -> None:
+    """Load layers + (embedding / final norm / LM head, if owned) of a stage from a checkpoint.
+    ``keep_fp8_block`` (the "fp8_block" mode): the decoder-layer linears of a 128 x 128
+    block-scaled FP8 checkpoint keep their stored bytes."""
     spec = stage.spec
     files = _weight_files(model_name, cache_dir, token)
     needed_prefixes = []
@@ -212,7 +220,11 @@ def load_stage_weights(stage: CausalLMStage, model_name: str, cache_dir=None, to
         extra = {"embed": ["model.embed_tokens.weight"],
                  "head": ["model.norm.weight", "lm_head.weight"]}
     for layer in stage.block.layers:
-        layer.load_hf_state_dict(get_block_state_dict(model_name, layer.layer_idx, cache_dir, token, lp))
+        sd = get_block_state_dict(model_name, layer.layer_idx, cache_dir, token, lp)
+        if keep_fp8_block and spec.arch == "llama":
+            layer.load_hf_state_dict(sd, keep_fp8_block=True)
+        else:
+            layer.load_hf_state_dict(sd)
     want = []
     if stage.embed is not None:
         want += extra["embed"]
@@ -303,7 +315,7 @@ def build_stage(model: str, start: int, end: int, device=None, dtype=torch.bfloa
     if random_init and checkpoint is None:
         stage.init_random(seed)
     else:
-        load_stage_weights(stage, checkpoint or model)
+        load_stage_weights(stage, checkpoint or model, keep_fp8_block=quantize == "fp8_block")
     stage.quantize(quantize, int8_threshold)
     return stage
 
