@@ -33,15 +33,13 @@ KERNEL_SOURCES = ["kernels/norm.hip", "kernels/activation.hip", "kernels/rope_ca
                   "kernels/quant.hip",
                   "kernels/gemv.hip", "kernels/gemm_tile.hip", "kernels/gemm4.hip",
                   "kernels/gemm_fp4.hip", "kernels/gemm_fp4_small.hip", "kernels/gemm_fp8_small.hip",
-                  "kernels/moe.hip", "kernels/moe_tile.hip", "kernels/moe_tile_mx.hip",
-                  "kernels/moe_tile_f8.hip", "kernels/moe_fp8_block.hip",
-                  "kernels/moe_tile_fp8_block.hip", "kernels/moe_tile_f8_block.hip",
+                  "kernels/moe.hip", "kernels/moe_tile.hip", "kernels/moe_tile_scaled.hip",
+                  "kernels/moe_fp8_block.hip", "kernels/moe_tile_fp8_block.hip",
                   "kernels/gemm_fp8_block_small.hip", "kernels/gemm_fp8_block_tile.hip",
                   "kernels/int8_outlier.hip", "kernels/digest.hip"]
 # sources compiled without packed fp32 instructions (v_pk_add/mul/fma_f32): scalar fp32 codegen
-NO_PACKED_FP32 = {"kernels/moe_tile_mx.hip", "kernels/moe_tile_f8.hip",
-                  "kernels/moe_fp8_block.hip", "kernels/moe_tile_fp8_block.hip",
-                  "kernels/moe_tile_f8_block.hip", "kernels/gemm_fp8_block_small.hip",
+NO_PACKED_FP32 = {"kernels/moe_tile_scaled.hip", "kernels/moe_fp8_block.hip",
+                  "kernels/moe_tile_fp8_block.hip", "kernels/gemm_fp8_block_small.hip",
                   "kernels/gemm_fp8_block_tile.hip"}
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 TORCH_SOURCES = ["bindings.hip", "comm/rccl_p2p.hip", "comm/streams.hip"]

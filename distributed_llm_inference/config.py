@@ -760,14 +760,14 @@ class KernelPolicy:
     # experts": 3.6-4.9x at 2048-8192 rows for fp8, 3.1-4.0x for MXFP4)
     moe_tile_rows_q: int = 0
     # sparse MoE, MXFP4 experts: where moe_tile_rows_q sends them to the tiles, run both products
-    # on the block-scaled fp4 x fp8 MFMA (csrc/kernels/moe_tile_mx.hip; x and h quantised to MX
+    # on the block-scaled fp4 x fp8 MFMA (csrc/kernels/moe_tile_scaled.hip; x and h quantised to MX
     # fp8 with row-major scales first) instead of widening the weight to bf16.  Experimental and
     # off: it changes the numerics of those products (fp8 activation rounding; docs/kernels.md
     # "Sparse MoE: block-scaled tile GEMM").  bf16 and fp8 experts ignore it, and so does every
     # call that moe_tile_rows_q leaves on the weight-streaming kernel
     moe_tile_mx: bool = False
     # sparse MoE, fp8 experts: where moe_tile_rows_q sends them to the tiles, run both products
-    # on the block-scaled MFMA with both operands fp8 (csrc/kernels/moe_tile_f8.hip; x and h
+    # on the block-scaled MFMA with both operands fp8 (csrc/kernels/moe_tile_scaled.hip; x and h
     # quantised to MX fp8 with row-major scales first, the weight's fp32 row scale applied in the
     # epilogue) instead of widening the weight to bf16.  Experimental and off: it changes the
     # numerics of those products (fp8 activation rounding; docs/kernels.md "Sparse MoE:
@@ -776,7 +776,7 @@ class KernelPolicy:
     moe_tile_f8: bool = False
     # sparse MoE, block-scaled fp8 experts ("fp8_block"): where moe_tile_rows_q sends them to the
     # tiles, run both products on the block-scaled MFMA with both operands fp8
-    # (csrc/kernels/moe_tile_f8_block.hip; x and h quantised to MX fp8 with row-major scales
+    # (csrc/kernels/moe_tile_scaled.hip; x and h quantised to MX fp8 with row-major scales
     # first, the weight's fp32 block scale folded in per k-step) instead of widening the weight to
     # bf16.  Experimental and off: it changes the numerics of those products (fp8 activation
     # rounding; docs/kernels.md "Sparse MoE: block-scaled tile GEMM, block-scaled fp8 experts").

@@ -1332,96 +1332,38 @@ void moe_tile_gemm(Tensor out, Tensor x, Tensor w, Tensor sorted_pairs, Tensor e
                                      cur_stream()), "moe_tile_gemm");
 }
 
-// MXFP4 experts x MX fp8 activations on the block-scaled MFMA (moe_tile_mx.hip): a_q e4m3 bytes
-// [R, K] with row-major e8m0 scales a_sc [R, K / 128] (quant_mx_rows); R = T for gate|up (gathered
-// by token), R >= T k for down.  Everything is checked before the launch
-void moe_tile_gemm_mx(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sorted_pairs,
-                      Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
-                      int64_t epilogue, optional<Tensor> scale) {
-  CHECK_IN(out); CHECK_IN(a_q); CHECK_IN(a_sc);
-  CHECK_BF16(out);
-  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
-  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
-  const ExpertArgs e = check_expert_weights("moe_tile_gemm_mx", w, scale, a_q.device());
-  TORCH_CHECK(e.w.format == dli::kExpertFp4, "moe_tile_gemm_mx: MXFP4 expert weights only (uint8 "
-              "nibbles with w_block_scale); bf16 and fp8 experts run on moe_tile_gemm");
-  TORCH_CHECK(out.dim() == 2 && a_q.dim() == 2 && a_q.element_size() == 1,
-              "moe_tile_gemm_mx: out 2-D, a_q = e4m3 bytes [R, K]");
-  TORCH_CHECK(e.K % 128 == 0, "moe_tile_gemm_mx: needs K % 128 == 0");
-  TORCH_CHECK(e.K <= dli::moe_tile_mx_max_k(), "moe_tile_gemm_mx: K = ", e.K, " exceeds the ",
-              dli::moe_tile_mx_max_k(), " whose activation scales the kernel's LDS slot holds");
-  check_moe_tile("moe_tile_gemm_mx", out, a_q, w, sorted_pairs, expert_count, expert_offset, T, k,
-                 epilogue, e.K);
-  TORCH_CHECK(epilogue == 1 || a_q.size(0) == T,
-              "moe_tile_gemm_mx: gate|up takes x quantised once per token, a_q [T, K]");
-  TORCH_CHECK(a_sc.scalar_type() == at::kByte && a_sc.dim() == 2 &&
-                  a_sc.size(0) == a_q.size(0) && a_sc.size(1) == e.K / 128 &&
-                  a_sc.device() == a_q.device(),
-              "moe_tile_gemm_mx: a_sc = uint8 e8m0 [R, K / 128], row-major, on a_q's device");
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(a_q.device());
-  check_rc(dli::launch_moe_tile_gemm_mx(bp(out), static_cast<const uint8_t*>(a_q.data_ptr()),
-                                        a_sc.data_ptr<uint8_t>(), e.w,
-                                        sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
-                                        expert_offset.data_ptr<int>(), (int)T, (int)e.E, (int)k,
-                                        (int)e.N, (int)e.K, (int)epilogue, cur_stream()),
-           "moe_tile_gemm_mx");
-}
-
-// fp8 experts x MX fp8 activations on the block-scaled MFMA (moe_tile_f8.hip): a_q / a_sc as for
-// moe_tile_gemm_mx, w e4m3fn [E, N, K] with scale fp32 [E, N].  Everything is checked before the
-// launch
-void moe_tile_gemm_f8(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sorted_pairs,
-                      Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
-                      int64_t epilogue, optional<Tensor> scale) {
-  CHECK_IN(out); CHECK_IN(a_q); CHECK_IN(a_sc);
-  CHECK_BF16(out);
-  CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
-  CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
-  const ExpertArgs e = check_expert_weights("moe_tile_gemm_f8", w, scale, a_q.device());
-  TORCH_CHECK(e.w.format == dli::kExpertFp8, "moe_tile_gemm_f8: fp8 expert weights only (e4m3fn "
-              "with an fp32 w_scale [E, N]; block-scaled fp8 experts run on moe_tile_gemm); MXFP4 experts run on moe_tile_gemm_mx, bf16 experts on "
-              "moe_tile_gemm");
-  TORCH_CHECK(out.dim() == 2 && a_q.dim() == 2 && a_q.element_size() == 1,
-              "moe_tile_gemm_f8: out 2-D, a_q = e4m3 bytes [R, K]");
-  TORCH_CHECK(e.K % 128 == 0, "moe_tile_gemm_f8: needs K % 128 == 0");
-  TORCH_CHECK(e.K <= dli::moe_tile_f8_max_k(), "moe_tile_gemm_f8: K = ", e.K, " exceeds the ",
-              dli::moe_tile_f8_max_k(), " whose activation scales the kernel's LDS slot holds");
-  check_moe_tile("moe_tile_gemm_f8", out, a_q, w, sorted_pairs, expert_count, expert_offset, T, k,
-                 epilogue, e.K);
-  TORCH_CHECK(epilogue == 1 || a_q.size(0) == T,
-              "moe_tile_gemm_f8: gate|up takes x quantised once per token, a_q [T, K]");
-  TORCH_CHECK(a_sc.scalar_type() == at::kByte && a_sc.dim() == 2 &&
-                  a_sc.size(0) == a_q.size(0) && a_sc.size(1) == e.K / 128 &&
-                  a_sc.device() == a_q.device(),
-              "moe_tile_gemm_f8: a_sc = uint8 e8m0 [R, K / 128], row-major, on a_q's device");
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(a_q.device());
-  check_rc(dli::launch_moe_tile_gemm_f8(bp(out), static_cast<const uint8_t*>(a_q.data_ptr()),
-                                        a_sc.data_ptr<uint8_t>(), e.w,
-                                        sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
-                                        expert_offset.data_ptr<int>(), (int)T, (int)e.E, (int)k,
-                                        (int)e.N, (int)e.K, (int)epilogue, cur_stream()),
-           "moe_tile_gemm_f8");
-}
-
-// block-scaled fp8 experts x MX fp8 activations on the block-scaled MFMA (moe_tile_f8_block.hip):
-// a_q / a_sc as for moe_tile_gemm_mx, w e4m3fn [E, N, K] with scale fp32 [E, N / 16, K / 128] as
-// stored.  Everything is checked before the launch
-void moe_tile_gemm_f8_block(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sorted_pairs,
-                            Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
-                            int64_t epilogue, optional<Tensor> scale) {
-  const char* what = "moe_tile_gemm_f8_block";
+// Quantised experts x MX fp8 activations on the block-scaled MFMA (moe_tile_scaled.hip), one entry
+// per weight format: moe_tile_gemm_mx (FORMAT = kExpertFp4: w uint8 nibbles [E, N, K / 2] with
+// w_block_scale), moe_tile_gemm_f8 (kExpertFp8: w e4m3fn [E, N, K] with scale fp32 [E, N]) and
+// moe_tile_gemm_f8_block (kExpertFp8Block: w e4m3fn [E, N, K] with scale fp32
+// [E, N / 16, K / 128] as stored).  a_q e4m3 bytes [R, K] with row-major e8m0 scales a_sc
+// [R, K / 128] (quant_mx_rows); R = T for gate|up (gathered by token), R >= T k for down.
+// Everything is checked before the launch
+template <int FORMAT>
+void moe_tile_gemm_scaled(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tensor sorted_pairs,
+                          Tensor expert_count, Tensor expert_offset, int64_t T, int64_t k,
+                          int64_t epilogue, optional<Tensor> scale) {
+  const char* what = FORMAT == dli::kExpertFp4   ? "moe_tile_gemm_mx"
+                     : FORMAT == dli::kExpertFp8 ? "moe_tile_gemm_f8"
+                                                 : "moe_tile_gemm_f8_block";
   CHECK_IN(out); CHECK_IN(a_q); CHECK_IN(a_sc);
   CHECK_BF16(out);
   CHECK_IN(sorted_pairs); CHECK_IN(expert_count); CHECK_IN(expert_offset);
   CHECK_I32(sorted_pairs); CHECK_I32(expert_count); CHECK_I32(expert_offset);
   const ExpertArgs e = check_expert_weights(what, w, scale, a_q.device());
-  TORCH_CHECK(e.w.format == dli::kExpertFp8Block, what, ": block-scaled fp8 expert weights only "
-              "(e4m3fn with an fp32 block scale [E, N / 16, K / 128]); per-row fp8 experts run on "
-              "moe_tile_gemm_f8, MXFP4 experts on moe_tile_gemm_mx, bf16 experts on moe_tile_gemm");
+  TORCH_CHECK(e.w.format == FORMAT, what, ": takes ",
+              FORMAT == dli::kExpertFp4   ? "MXFP4 (uint8 nibbles with w_block_scale)"
+              : FORMAT == dli::kExpertFp8 ? "fp8 (e4m3fn with an fp32 w_scale [E, N])"
+                                          : "block-scaled fp8 (e4m3fn with an fp32 block scale "
+                                            "[E, N / 16, K / 128])",
+              " expert weights only; MXFP4 experts run on moe_tile_gemm_mx, per-row fp8 experts "
+              "on moe_tile_gemm_f8, block-scaled fp8 experts on moe_tile_gemm_f8_block, bf16 "
+              "experts on moe_tile_gemm");
   TORCH_CHECK(out.dim() == 2 && a_q.dim() == 2 && a_q.element_size() == 1,
               what, ": out 2-D, a_q = e4m3 bytes [R, K]");
-  TORCH_CHECK(e.K <= dli::moe_tile_f8_block_max_k(), what, ": K = ", e.K, " exceeds the ",
-              dli::moe_tile_f8_block_max_k(),
+  TORCH_CHECK(e.K % 128 == 0, what, ": needs K % 128 == 0");
+  TORCH_CHECK(e.K <= dli::moe_tile_scaled_max_k(), what, ": K = ", e.K, " exceeds the ",
+              dli::moe_tile_scaled_max_k(),
               " whose activation scales the kernel's LDS slot holds");
   check_moe_tile(what, out, a_q, w, sorted_pairs, expert_count, expert_offset, T, k, epilogue,
                  e.K);
@@ -1432,7 +1374,7 @@ void moe_tile_gemm_f8_block(Tensor out, Tensor a_q, Tensor a_sc, Tensor w, Tenso
                   a_sc.device() == a_q.device(),
               what, ": a_sc = uint8 e8m0 [R, K / 128], row-major, on a_q's device");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(a_q.device());
-  check_rc(dli::launch_moe_tile_gemm_f8_block(
+  check_rc(dli::launch_moe_tile_gemm_scaled(
                bp(out), static_cast<const uint8_t*>(a_q.data_ptr()), a_sc.data_ptr<uint8_t>(),
                e.w, sorted_pairs.data_ptr<int>(), expert_count.data_ptr<int>(),
                expert_offset.data_ptr<int>(), (int)T, (int)e.E, (int)k, (int)e.N, (int)e.K,
@@ -1767,31 +1709,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"), py::arg("scale") = py::none());
-  m.def("moe_tile_gemm_mx", &moe_tile_gemm_mx,
+  m.def("moe_tile_gemm_mx", &moe_tile_gemm_scaled<dli::kExpertFp4>,
         "grouped block-scaled MFMA tile GEMM: MXFP4 experts x MX fp8 activations with row-major "
         "scales (0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("a_q"), py::arg("a_sc"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"), py::arg("scale") = py::none());
-  m.def("moe_tile_mx_max_k", []() { return dli::moe_tile_mx_max_k(); },
-        "largest K of moe_tile_gemm_mx");
-  m.def("moe_tile_gemm_f8", &moe_tile_gemm_f8,
+  m.def("moe_tile_mx_max_k", &dli::moe_tile_scaled_max_k, "largest K of moe_tile_gemm_mx");
+  m.def("moe_tile_gemm_f8", &moe_tile_gemm_scaled<dli::kExpertFp8>,
         "grouped block-scaled MFMA tile GEMM, both operands fp8: fp8 experts with fp32 row scales "
         "x MX fp8 activations with row-major scales (0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("a_q"), py::arg("a_sc"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"), py::arg("scale") = py::none());
-  m.def("moe_tile_f8_max_k", []() { return dli::moe_tile_f8_max_k(); },
-        "largest K of moe_tile_gemm_f8");
-  m.def("moe_tile_gemm_f8_block", &moe_tile_gemm_f8_block,
+  m.def("moe_tile_f8_max_k", &dli::moe_tile_scaled_max_k, "largest K of moe_tile_gemm_f8");
+  m.def("moe_tile_gemm_f8_block", &moe_tile_gemm_scaled<dli::kExpertFp8Block>,
         "grouped block-scaled MFMA tile GEMM, both operands fp8: fp8 experts with fp32 scales per "
         "16 rows x 128 k, folded in per k-step, x MX fp8 activations with row-major scales "
         "(0: gate|up + SwiGLU, 1: down)",
         py::arg("out"), py::arg("a_q"), py::arg("a_sc"), py::arg("w"), py::arg("sorted_pairs"),
         py::arg("expert_count"), py::arg("expert_offset"), py::arg("T"), py::arg("k"),
         py::arg("epilogue"), py::arg("scale") = py::none());
-  m.def("moe_tile_f8_block_max_k", []() { return dli::moe_tile_f8_block_max_k(); },
-        "largest K of moe_tile_gemm_f8_block");
+  m.def("moe_tile_f8_block_max_k", &dli::moe_tile_scaled_max_k, "largest K of moe_tile_gemm_f8_block");
   m.def("quant_mx_rows", &quant_mx_rows,
         "MX fp8 quantiser with row-major scales: bf16 [M, K] -> e4m3 bytes + e8m0 [M, K / 128]",
         py::arg("q"), py::arg("sc"), py::arg("x"));

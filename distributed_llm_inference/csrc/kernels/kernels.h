@@ -262,40 +262,24 @@ int moe_tile_gemm_capacity(int T, int E, int k);
 int launch_moe_tile_gemm(bf16* out, const bf16* x, ExpertW W, const int* sorted_pairs,
                          const int* expert_count, const int* expert_offset, int T, int E, int k,
                          int N, int K, int epilogue, hipStream_t stream);
-// The same two products for MXFP4 experts on the block-scaled MFMA (moe_tile_mx.hip): the weight
-// nibbles times MX fp8 activations a_q [R, K] e4m3 bytes with row-major e8m0 scales a_sc
-// [R, K / 128] (launch_quant_mx_rows), both scale sets on the MFMA's scale operands.  Epilogue 0
-// gathers a_q / a_sc by token (R = T: x quantised once per token), epilogue 1 reads rows
-// start + r (R >= P: h quantised in sorted order).  W.format must be kExpertFp4 (else -6);
-// N % 128 == 0, K % 128 == 0, K <= moe_tile_mx_max_k() (else -2); grid and other codes as above
-int moe_tile_mx_max_k();
-int launch_moe_tile_gemm_mx(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
-                            const int* sorted_pairs, const int* expert_count,
-                            const int* expert_offset, int T, int E, int k, int N, int K,
-                            int epilogue, hipStream_t stream);
-// The same two products for block-scaled fp8 experts on the block-scaled MFMA with both operands
-// fp8 (moe_tile_f8_block.hip): the stored e4m3 weight bytes times MX fp8 activations (a_q / a_sc
-// as above, gathered the same way), the activation scales on the MFMA's scale operand.  Every
-// MFMA covers one 128-k block of one 16-row group and starts from zero; its result times the
-// block's fp32 scale W.scale [E, N / 16, K / 128] is added to the fp32 accumulator, so nothing
-// is left to scale in the epilogue.  W.format must be kExpertFp8Block (else -6); N % 128 == 0,
-// K % 128 == 0, K <= moe_tile_f8_block_max_k() (else -2); grid and other codes as above
-int moe_tile_f8_block_max_k();
-int launch_moe_tile_gemm_f8_block(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
-                                  const int* sorted_pairs, const int* expert_count,
-                                  const int* expert_offset, int T, int E, int k, int N, int K,
-                                  int epilogue, hipStream_t stream);
-// The same two products for fp8 experts on the block-scaled MFMA with both operands fp8
-// (moe_tile_f8.hip): the stored e4m3 weight bytes times MX fp8 activations (a_q / a_sc as above,
-// gathered the same way), the activation scales on the MFMA's scale operand, the fp32 row scale
-// W.scale [E, N] applied to the fp32 sum in the epilogue before any rounding.  W.format must be
-// kExpertFp8 (else -6); N % 128 == 0, K % 128 == 0, K <= moe_tile_f8_max_k() (else -2); grid and
-// other codes as above
-int moe_tile_f8_max_k();
-int launch_moe_tile_gemm_f8(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
-                            const int* sorted_pairs, const int* expert_count,
-                            const int* expert_offset, int T, int E, int k, int N, int K,
-                            int epilogue, hipStream_t stream);
+// The same two products for quantised experts on the block-scaled MFMA (moe_tile_scaled.hip): the
+// stored weight bytes times MX fp8 activations a_q [R, K] e4m3 bytes with row-major e8m0 scales
+// a_sc [R, K / 128] (launch_quant_mx_rows), the activation scales on the MFMA's scale operand.
+// Epilogue 0 gathers a_q / a_sc by token (R = T: x quantised once per token), epilogue 1 reads
+// rows start + r (R >= P: h quantised in sorted order).  By W.format:
+//   MXFP4: the weight nibbles' e8m0 scales go on the MFMA's other scale operand;
+//   fp8: the fp32 row scale W.scale [E, N] is applied to the fp32 sum after the k-loop, before
+//     any rounding;
+//   block-scaled fp8: every MFMA covers one 128-k block of one 16-row group and starts from
+//     zero; its result times the block's fp32 scale W.scale [E, N / 16, K / 128] is added to the
+//     fp32 accumulator, so nothing is left to scale in the epilogue;
+//   bf16: -6 (moe_tile.hip's).
+// N % 128 == 0, K % 128 == 0, K <= moe_tile_scaled_max_k() (else -2); grid and other codes as above
+int moe_tile_scaled_max_k();
+int launch_moe_tile_gemm_scaled(bf16* out, const uint8_t* a_q, const uint8_t* a_sc, ExpertW W,
+                                const int* sorted_pairs, const int* expert_count,
+                                const int* expert_offset, int T, int E, int k, int N, int K,
+                                int epilogue, hipStream_t stream);
 // out [T, H] = bf16(sum_slot w[t, slot] * y[t k + slot]) in fp32, slot order; H % 8 == 0
 int launch_moe_combine(bf16* out, const bf16* y, const float* w, int T, int k, int H,
                        hipStream_t stream);
@@ -318,7 +302,7 @@ int gemm_fp4_max_ktiles();
 // K / 128 * ceil(rows / 64) * 64 bytes; rows past `rows` hold 127): ops.mx_quantize's rule
 int launch_quant_mx(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K, hipStream_t stream);
 // the same bytes and exponents with row-major scales sc [rows, K / 128] (no padding), for
-// consumers that gather rows (moe_tile_mx.hip)
+// consumers that gather rows (moe_tile_scaled.hip)
 int launch_quant_mx_rows(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K,
                          hipStream_t stream);
 // one-wave-per-SIMD 256x256 GEMM (gemm4.hip); epilogue 0 bf16, 1 fp32 partials, 2 SwiGLU,

@@ -2,9 +2,12 @@
 // template and its launcher, shared by moe_tile.hip (bf16, per-row fp8 and MXFP4 experts) and
 // moe_tile_fp8_block.hip (block-scaled fp8 experts, whose in-loop rescale is fp32 vector
 // arithmetic and is compiled without packed fp32 instructions: a translation unit of its own, so
-// that the other three formats keep the code they have).
+// that the other three formats keep the code they have).  The tile geometry, the prologue that
+// finds the tile, the epilogues and the launcher's checks are moe_tile_parts.h's.
 #pragma once
-#include "kernels.h"
+#include <climits>
+
+#include "moe_tile_parts.h"
 
 namespace dli {
 
@@ -17,15 +20,9 @@ int launch_moe_tile_fp8_block(bf16* out, const bf16* x, const void* W, const voi
 
 namespace {
 
-constexpr int kMaxExperts = 256;
-constexpr int kMaxTopK = 8;
-constexpr int kTM = 128;          // activation rows per tile
-constexpr int kTN = 128;          // weight rows per workgroup
 constexpr int kBK = 64;           // k per step
-constexpr int kThreads = 256;
 constexpr int kOp = 128 * 128;    // bytes of one staged operand tile
 
-enum MoeEp { kMoeGateUp = 0, kMoeDown = 1 };
 enum TileWf { kTileBf16 = 0, kTileFp8 = 1, kTileFp4 = 2, kTileFp8Block = 3 };
 
 // fp8 bytes in LDS, whichever scales go with them
@@ -48,40 +45,10 @@ moe_tile_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ Wv,
   __shared__ __attribute__((aligned(1024))) char smem[2 * kBuf];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = blockIdx.y, nb = blockIdx.x;
+  const int nb = blockIdx.x;
 
-  // ---- which expert, which rows: the wave's prefix sum over ceil(count / 128) ----
-  int cnt[4], nt[4], mine_tiles = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int j = 4 * lane + q;
-    cnt[q] = j < E ? min(max(expert_count[j], 0), P) : 0;
-    nt[q] = (cnt[q] + kTM - 1) / kTM;
-    mine_tiles += nt[q];
-  }
-  int incl = mine_tiles;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  if (tile >= __shfl(incl, 63, 64)) return;   // before any DMA or barrier; the same in every wave
-  int rem = tile - (incl - mine_tiles), e_l = 4 * lane, c_l = cnt[0];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    if (e_l == 4 * lane + q && rem >= nt[q]) {
-      rem -= nt[q];
-      e_l = 4 * lane + q + 1;
-      c_l = cnt[q + 1];
-    }
-  }
-  const unsigned long long own = __ballot(incl - mine_tiles <= tile && tile < incl);
-  const int owner = own ? __builtin_ctzll(own) : 0;   // exactly one lane (tile < the sum)
-  const int e = min(max(__builtin_amdgcn_readlane(e_l, owner), 0), E - 1);
-  const int ti = max(__builtin_amdgcn_readlane(rem, owner), 0);
-  const int ce = __builtin_amdgcn_readlane(c_l, owner);
-  const int rows = min(max(ce - kTM * ti, 1), min(kTM, P));
-  const int start = min(max(expert_offset[e] + kTM * ti, 0), P - rows);
+  int e, rows, start;
+  if (!moe_tile_locate(expert_count, expert_offset, E, P, blockIdx.y, lane, e, rows, start)) return;
   const int* pairs = sorted_pairs + start;
   const bf16* We = static_cast<const bf16*>(Wv) + (size_t)e * N * K;   // the bf16 experts only
   const int n0 = nb * kTN;
@@ -278,68 +245,27 @@ moe_tile_gemm_kernel(const bf16* __restrict__ x, const void* __restrict__ Wv,
     }
   }
 
-  // ---- epilogue: acc[a][b][i] = y[m = 64 wc + 16 b + fr][n = n0 + 64 wr + 16 a + 4 g + i] ----
-  if constexpr (EPI == kMoeGateUp) {
-    const int I = N >> 1;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int m = 64 * wc + 16 * b + fr;
-      if (m >= rows) continue;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        bf16x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float gt = (float)(bf16)acc[2 * p][b][i];
-          const float up = (float)(bf16)acc[2 * p + 1][b][i];
-          o[i] = (bf16)(silu(gt) * up);
-        }
-        // weight rows 32 q .. 32 q + 31 are gate | up of output columns 16 q .. 16 q + 15
-        const int col = ((n0 + 64 * wr + 32 * p) >> 1) + 4 * g;
-        *reinterpret_cast<bf16x4*>(out + (size_t)(start + m) * I + col) = o;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int m = 64 * wc + 16 * b + fr;
-      if (m >= rows) continue;
-      const size_t dst = (size_t)min(max(pairs[m], 0), P - 1);
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        bf16x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = (bf16)acc[a][b][i];
-        *reinterpret_cast<bf16x4*>(out + dst * N + n0 + 64 * wr + 16 * a + 4 * g) = o;
-      }
-    }
-  }
+  moe_tile_epilogue<EPI>(acc, out, pairs, rows, start, P, N, n0, wr, wc, fr, g);
 }
 
 template <int WF>
 int launch_tile(bf16* out, const bf16* x, const void* W, const void* wscale,
                 const int* sorted_pairs, const int* expert_count, const int* expert_offset, int T,
                 int E, int k, int N, int K, int epilogue, hipStream_t stream) {
-  if (T <= 0 || E <= 0 || E > kMaxExperts || k <= 0 || k > kMaxTopK) return -1;
-  if (N <= 0 || N % kTN != 0 || K <= 0 || K % kBK != 0) return -2;
-  if ((WF == kTileFp4 || WF == kTileFp8Block) && K % 128 != 0) return -2;
-  if ((long)T * k > (1L << 30)) return -3;
-  const int cap = moe_tile_gemm_capacity(T, E, k);
-  if (cap <= 0 || cap > 65535) return -3;
-  if (out == nullptr || x == nullptr || W == nullptr || sorted_pairs == nullptr ||
-      expert_count == nullptr || expert_offset == nullptr)
-    return -5;
-  if (WF != kTileBf16 && wscale == nullptr) return -5;
-  const dim3 grid(N / kTN, cap);
+  const int rc = moe_tile_check_args(
+      T, E, k, N, K, WF == kTileFp4 || WF == kTileFp8Block ? 128 : kBK, INT_MAX, epilogue,
+      out != nullptr && x != nullptr && W != nullptr && sorted_pairs != nullptr &&
+          expert_count != nullptr && expert_offset != nullptr &&
+          (WF == kTileBf16 || wscale != nullptr));
+  if (rc != 0) return rc;
+  const dim3 grid(N / kTN, moe_tile_gemm_capacity(T, E, k));
   const int P = T * k;
   if (epilogue == kMoeGateUp)
     moe_tile_gemm_kernel<kMoeGateUp, WF><<<grid, kThreads, 0, stream>>>(
         x, W, out, sorted_pairs, expert_count, expert_offset, E, k, P, N, K, wscale);
-  else if (epilogue == kMoeDown)
+  else
     moe_tile_gemm_kernel<kMoeDown, WF><<<grid, kThreads, 0, stream>>>(
         x, W, out, sorted_pairs, expert_count, expert_offset, E, k, P, N, K, wscale);
-  else
-    return -4;
   return 0;
 }
 

@@ -321,7 +321,7 @@ int launch_quant_mx(uint8_t* q, uint8_t* sc, const bf16* x, int rows, int K, hip
 }
 
 // The same quantiser with ROW-MAJOR scales sc [rows, K / 128], for consumers that gather rows
-// (moe_tile_mx.hip): the same 16 lanes per block and the same arithmetic, so bytes and exponents
+// (moe_tile_scaled.hip): the same 16 lanes per block and the same arithmetic, so bytes and exponents
 // are quant_mx_kernel's bit for bit; the scale of block blk is byte blk, and there is no padding.
 __global__ void __launch_bounds__(256) quant_mx_rows_kernel(uint8_t* __restrict__ q,
                                                             uint8_t* __restrict__ sc,

@@ -1102,7 +1102,7 @@ def quant_mx(h: torch.Tensor) -> MxFp8:
 
 class MxFp8Rows:
     """:class:`MxFp8` values with the scales row-major: ``q [M, K]`` e4m3 and ``sc [M, K / 128]``
-    uint8 e8m0, so a consumer that gathers rows (moe_tile_mx.hip) takes a row's scales with it."""
+    uint8 e8m0, so a consumer that gathers rows (moe_tile_scaled.hip) takes a row's scales with it."""
 
     __slots__ = ("q", "sc")
 
@@ -1537,9 +1537,9 @@ MoERouting = ref.MoERouting
 ExpertWeights = ref.ExpertWeights
 MOE_MAX_EXPERTS = ref.MOE_MAX_EXPERTS
 MOE_MAX_TOPK = ref.MOE_MAX_TOPK
-MOE_TILE_MX_MAX_K = 16384  # moe_tile_mx.hip kMaxKt * 128: the activation scales' LDS slot
-MOE_TILE_F8_MAX_K = 16384  # moe_tile_f8.hip kMaxKt * 128: the same slot
-MOE_TILE_F8_BLOCK_MAX_K = 16384  # moe_tile_f8_block.hip kMaxKt * 128: the same slot
+MOE_TILE_MX_MAX_K = 16384  # moe_tile_scaled.hip kMaxKt * 128: the activation scales' LDS slot
+MOE_TILE_F8_MAX_K = 16384  # moe_tile_scaled.hip kMaxKt * 128: the same slot
+MOE_TILE_F8_BLOCK_MAX_K = 16384  # moe_tile_scaled.hip kMaxKt * 128: the same slot
 moe_tile_capacity = ref.moe_tile_capacity
 
 
@@ -1614,7 +1614,7 @@ def moe_uses_tiles(T: int, k: int, E: int, weight_format: str, device) -> bool:
 
 
 def moe_uses_mx(T: int, k: int, E: int, weight_format: str, device) -> bool:
-    """Whether that call runs on the block-scaled fp4 x fp8 tile GEMM (moe_tile_mx.hip, MX fp8
+    """Whether that call runs on the block-scaled fp4 x fp8 tile GEMM (moe_tile_scaled.hip, MX fp8
     activations): it goes to the tiles (:func:`moe_uses_tiles`), ``KernelPolicy.moe_tile_mx`` is
     set and the experts are MXFP4."""
     return bool(weight_format == "mxfp4" and policy().moe_tile_mx
@@ -1622,7 +1622,7 @@ def moe_uses_mx(T: int, k: int, E: int, weight_format: str, device) -> bool:
 
 
 def moe_uses_f8(T: int, k: int, E: int, weight_format: str, device) -> bool:
-    """Whether that call runs on the block-scaled fp8 x fp8 tile GEMM (moe_tile_f8.hip, MX fp8
+    """Whether that call runs on the block-scaled fp8 x fp8 tile GEMM (moe_tile_scaled.hip, MX fp8
     activations): it goes to the tiles (:func:`moe_uses_tiles`), ``KernelPolicy.moe_tile_f8`` is
     set and the experts are fp8."""
     return bool(weight_format == "fp8" and policy().moe_tile_f8
@@ -1631,7 +1631,7 @@ def moe_uses_f8(T: int, k: int, E: int, weight_format: str, device) -> bool:
 
 def moe_uses_f8_block(T: int, k: int, E: int, weight_format: str, device) -> bool:
     """Whether that call runs on the fp8 x fp8 tile GEMM of block-scaled fp8 experts
-    (moe_tile_f8_block.hip, MX fp8 activations): it goes to the tiles (:func:`moe_uses_tiles`),
+    (moe_tile_scaled.hip, MX fp8 activations): it goes to the tiles (:func:`moe_uses_tiles`),
     ``KernelPolicy.moe_tile_f8_block`` is set and the experts are ``"fp8_block"``."""
     return bool(weight_format == "fp8_block" and policy().moe_tile_f8_block
                 and moe_uses_tiles(T, k, E, weight_format, device))
@@ -1672,8 +1672,8 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
     ``mx`` (MXFP4 and fp8 experts): True quantises the activations to MX fp8 with row-major
     scales (:func:`quant_mx_rows`; ``x`` may also be an :class:`MxFp8Rows` already) and multiplies
     them with the weights as they are stored on the block-scaled MFMA -- MXFP4 nibbles with both
-    scale sets on the instruction (moe_tile_mx.hip), fp8 bytes with the fp32 row scale applied to
-    the fp32 sum in the epilogue (moe_tile_f8.hip): N % 128 == 0, K % 128 == 0, K <= 16384, and
+    scale sets on the instruction (moe_tile_scaled.hip), fp8 bytes with the fp32 row scale applied to
+    the fp32 sum in the epilogue (moe_tile_scaled.hip): N % 128 == 0, K % 128 == 0, K <= 16384, and
     ``KernelPolicy.moe_tile_rows_q`` set, as for ``tiles=True``; anything else is a
     ``ValueError``, never another kernel.  The numerics are those of
     ``dequantize(mx_quantize(x))`` times the dequantised weights (fp8: the bytes, then the row
@@ -1686,7 +1686,7 @@ def moe_grouped_gemm(x, w, r: MoERouting, down: bool = False,
 
     ``f8_block`` (block-scaled fp8 experts): True quantises the activations the same way (or takes
     an :class:`MxFp8Rows`) and multiplies them with the stored e4m3 bytes on the block-scaled MFMA
-    (moe_tile_f8_block.hip).  One instruction covers one 128-k block of one 16-row group, so each
+    (moe_tile_scaled.hip).  One instruction covers one 128-k block of one 16-row group, so each
     starts from zero and its result times the block's fp32 scale is added to the fp32 sum: the
     numerics of ``dequantize(mx_quantize(x))`` times the dequantised weights in fp32 with the same
     epilogue rounding, which is what ``f8_block=True`` computes on the CPU.  N % 128 == 0,

@@ -70,12 +70,12 @@ does the quantised kernel follow its bytes?), plus the two products alone on eac
 ``vs_bf16_tile`` is the time ratio of a quantised tile candidate to its bf16 twin and
 ``weight_bytes_vs_bf16`` the ratio of the expert bytes behind it.  Results:
 ``<out>/moe_tile_fp8.json`` / ``<out>/moe_tile_fp4.json``.  ``--tile --fp4`` also times the
-block-scaled kernel (csrc/kernels/moe_tile_mx.hip) in the same interleaved rounds: ``moe_tile_mx``
+block-scaled kernel (csrc/kernels/moe_tile_scaled.hip) in the same interleaved rounds: ``moe_tile_mx``
 (route, quantise x, gate|up, quantise h, down, combine), ``gate_up_tile_mx`` / ``down_tile_mx`` on
 activations quantised beforehand, ``quant_x`` / ``quant_h`` (the quantiser passes alone), with
 ``vs_tile`` = time / the widening MXFP4 tile kernel's; the run is also kept as
 ``<out>/moe_tile_mx.json``.  ``--tile --fp8`` does the same for the fp8 x fp8 block-scaled kernel
-(csrc/kernels/moe_tile_f8.hip): ``moe_tile_f8``, ``gate_up_tile_f8`` / ``down_tile_f8``, ``quant_x``
+(csrc/kernels/moe_tile_scaled.hip): ``moe_tile_f8``, ``gate_up_tile_f8`` / ``down_tile_f8``, ``quant_x``
 / ``quant_h``, ``vs_tile`` against the widening fp8 tile kernel, kept as ``<out>/moe_tile_f8.json``.
 """
 import argparse
@@ -426,8 +426,8 @@ def bench_tile_q(torch, ops, F, name, rows, res, a):
             x, wgu[c], routes[c], out=hs[c], tiles=True)
         cands["down_tile_bf16"] = lambda c: ops.moe_grouped_gemm(
             hs[c], wd[c], routes[c], down=True, out=ys[c], tiles=True)
-        # the block-scaled kernel (moe_tile_mx.hip / moe_tile_f8.hip): the block, its products on
-        # activations quantised beforehand, and the two quantiser passes alone
+        # the block-scaled kernel (moe_tile_scaled.hip): the block, its products on activations
+        # quantised beforehand, and the two quantiser passes alone
         xq = ops.quant_mx_rows(x)
         hq = [ops.quant_mx_rows(hs[c]) for c in range(copies)]
         hm = [hs[c].clone() for c in range(copies)]
@@ -732,13 +732,13 @@ def main():
                         "(128-row tiles, moe_tile.hip; the weights widened at fragment-read time)",
             "moe_tile_bf16": "the bf16 tile GEMM on the dequantised weights",
             **({"moe_tile_mx": "route, quantise x to MX fp8 (row-major scales), gate|up, quantise "
-                               "h, down on the block-scaled fp4 x fp8 MFMA (moe_tile_mx.hip), "
+                               "h, down on the block-scaled fp4 x fp8 MFMA (moe_tile_scaled.hip), "
                                "combine; vs_tile = time / moe_tile's in the same run",
                 "gate_up_tile_mx / down_tile_mx, quant_x / quant_h":
                     "its two products on activations quantised beforehand, and the two "
                     "quantiser passes alone"} if a.fp4 else
                {"moe_tile_f8": "route, quantise x to MX fp8 (row-major scales), gate|up, quantise "
-                               "h, down on the block-scaled fp8 x fp8 MFMA (moe_tile_f8.hip), "
+                               "h, down on the block-scaled fp8 x fp8 MFMA (moe_tile_scaled.hip), "
                                "combine; vs_tile = time / moe_tile's in the same run",
                 "gate_up_tile_f8 / down_tile_f8, quant_x / quant_h":
                     "its two products on activations quantised beforehand, and the two "

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Block-scaled fp8 experts in prefill: the fp8 x fp8 tile GEMM (csrc/kernels/moe_tile_f8_block.hip,
+"""Block-scaled fp8 experts in prefill: the fp8 x fp8 tile GEMM (csrc/kernels/moe_tile_scaled.hip,
 MX fp8 activations) against the widening tile GEMM (csrc/kernels/moe_tile_fp8_block.hip, bf16
 activations) that runs today.  scripts/bench_moe.py's protocol and scripts/bench_mxfp4.py's helpers.
 

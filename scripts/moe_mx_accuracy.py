@@ -2,8 +2,8 @@
 """What MX fp8 activation rounding costs one MoE block with MXFP4 (default) or fp8 (``--fp8``)
 experts: the largest absolute error of the block output, relative to the output's largest
 magnitude, against an fp64 reference on the UNQUANTISED bf16 activations and the dequantised expert
-weights, for the widening tile kernel (moe_tile.hip) and the block-scaled one (moe_tile_mx.hip /
-moe_tile_f8.hip).  Random weights, one layer.
+weights, for the widening tile kernel (moe_tile.hip) and the block-scaled one
+(moe_tile_scaled.hip).  Random weights, one layer.
 
     python3 scripts/moe_mx_accuracy.py [--fp8] [--model qwen3-30b-a3b] [--tokens 2048]
 
@@ -22,7 +22,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="qwen3-30b-a3b")
     ap.add_argument("--tokens", type=int, default=2048)
-    ap.add_argument("--fp8", action="store_true", help="fp8 experts (moe_tile_f8.hip)")
+    ap.add_argument("--fp8", action="store_true", help="fp8 experts (moe_tile_scaled.hip)")
     a = ap.parse_args()
     spec = PRESETS[a.model]
     H, I, E, k = (spec.hidden_size, spec.moe_intermediate_size, spec.num_experts,

@@ -1,4 +1,4 @@
-"""The CPU side of moe_tile_f8_block.hip: ``moe_grouped_gemm(f8_block=True)``, the oracle of the
+"""The CPU side of moe_tile_scaled.hip: ``moe_grouped_gemm(f8_block=True)``, the oracle of the
 GPU path, ``moe_uses_f8_block`` and the ``KernelPolicy.moe_tile_f8_block`` knob."""
 import pytest
 import torch

@@ -1,12 +1,15 @@
-"""The fp8 x fp8 MFMA tile GEMM for block-scaled fp8 experts (csrc/kernels/moe_tile_f8_block.hip)
-on the GPU: exactly-summable operands bit for bit, random data against fp64, the MoE block under
-``KernelPolicy.moe_tile_f8_block`` (eager and in a captured graph) and the host checks."""
+"""The fp8 x fp8 MFMA tile GEMM for block-scaled fp8 experts (csrc/kernels/moe_tile_scaled.hip)
+on the GPU: exactly-summable operands bit for bit, random data against fp64, row independence, the
+MoE block under ``KernelPolicy.moe_tile_f8_block`` (eager and in a captured graph) and the host
+checks."""
 import copy
 
 import pytest
 import torch
 
 import moe_tile_cases as mc
+from moe_tile_cases import (bits as _bits, guarded as _guarded, products as _products,
+                            swiglu64 as _swiglu64)
 from distributed_llm_inference import ops
 from distributed_llm_inference.config import ModelSpec
 from distributed_llm_inference.models.llama.modules import MoEMLP
@@ -14,48 +17,18 @@ from distributed_llm_inference.ops.reference import expand_fp8_block_scale
 
 pytestmark = pytest.mark.gpu
 BF, FP8, U8 = torch.bfloat16, torch.float8_e4m3fn, torch.uint8
-SENT, G = -12345.0, 8
+SENT = mc.SENT
 E, K = mc.E, mc.K_TOP
 SHAPES = [(256, 128), (1152, 384)]
-ATOL, RTOL = 2e-2, 2e-2     # tests/test_moe_tile_q_gpu.py's oracle tolerance, elementwise
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 def _close(got, want):
-    err = (got.double() - want.double()).abs()
-    print(f"max err {float(err.max()):.4g} of {float(want.abs().max()):.4g}")
-    return float(want.abs().max()) > 0.5 and bool((err <= ATOL + RTOL * want.double().abs()).all())
+    return float(want.abs().max()) > 0.5 and mc.close(got, want)
 
 
 def _routing(gpu):
-    ids = mc.explicit_ids()
-    r = ops.moe_group(ids.to(gpu), torch.ones(ids.shape, device=gpu), E)
-    pairs = r.sorted_pairs.cpu().long()
+    ids, r, pairs = mc.routing(gpu)
     return ids, r, pairs, ids.reshape(-1).long()[pairs]       # .., the expert of sorted row j
-
-
-def _guarded(fn, rows, width, gpu):
-    buf = torch.full((G + rows + G, width), SENT, dtype=BF, device=gpu)
-    fn(buf[G:])
-    torch.cuda.synchronize()
-    assert bool((buf[:G] == SENT).all()) and bool((buf[G + rows:] == SENT).all()), "guard rows"
-    return buf[G:G + rows].cpu()
-
-
-def _products(rows, wd, e_row):
-    # fp64 [P, N]: row j of rows [P, K] times expert e_row[j] of wd [E, N, K]
-    out = torch.empty(rows.shape[0], wd.shape[1], dtype=torch.float64)
-    for e in range(E):
-        out[e_row == e] = rows[e_row == e] @ wd[e].t()
-    return out
-
-
-def _swiglu64(gu):
-    v = gu.reshape(gu.shape[0], -1, 2, 16)       # swiglu_interleave: 16 gate rows, 16 up rows
-    return (torch.nn.functional.silu(v[:, :, 0]) * v[:, :, 1]).reshape(gu.shape[0], -1)
 
 
 _dq = lambda w: w.w.float().double() * expand_fp8_block_scale(w.scale).double()
@@ -115,21 +88,46 @@ def test_layout_bit_exact_against_fp64_and_the_widening_kernel(gpu, H, I):
     assert _close(h, _swiglu64(gu))
 
 
+def _random_case(H, I, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(mc.explicit_ids().shape[0], H, generator=g).to(BF)
+    gu = ops.ExpertWeights.quantize((torch.randn(E, 2 * I, H, generator=g) / H ** 0.5).to(BF), "fp8_block")
+    dn = ops.ExpertWeights.quantize((torch.randn(E, H, I, generator=g) / I ** 0.5).to(BF), "fp8_block")
+    return x, gu, dn
+
+
+def _run(gpu, x, gu, dn, r):
+    with ops.kernel_policy(moe_tile_rows_q=32):
+        h = ops.moe_grouped_gemm(x.to(gpu), _to(gu, gpu), r, f8_block=True)
+        y = ops.moe_grouped_gemm(h, _to(dn, gpu), r, down=True, f8_block=True)
+    return h.cpu(), y.cpu()
+
+
 @pytest.mark.parametrize("H,I", SHAPES)
 def test_random_against_fp64_on_quantise_dequantised_operands(gpu, H, I):
     ids, r, pairs, e_row = _routing(gpu)
-    g = torch.Generator().manual_seed(H)
-    x = torch.randn(ids.shape[0], H, generator=g).to(BF)
-    gu = ops.ExpertWeights.quantize((torch.randn(E, 2 * I, H, generator=g) / H ** 0.5).to(BF), "fp8_block")
-    dn = ops.ExpertWeights.quantize((torch.randn(E, H, I, generator=g) / I ** 0.5).to(BF), "fp8_block")
-    with ops.kernel_policy(moe_tile_rows_q=32):
-        h = ops.moe_grouped_gemm(x.to(gpu), _to(gu, gpu), r, f8_block=True)
-        y = ops.moe_grouped_gemm(h, _to(dn, gpu), r, down=True, f8_block=True).cpu()
-    h = h.cpu()
+    x, gu, dn = _random_case(H, I, H)
+    h, y = _run(gpu, x, gu, dn, r)
     xd = ops.quant_mx_rows(x).dequantize().double()[pairs // K]
     want_y = torch.empty(ids.numel(), H, dtype=torch.float64)
     want_y[pairs] = _products(ops.quant_mx_rows(h).dequantize().double(), _dq(dn), e_row)
     assert _close(h, _swiglu64(_products(xd, _dq(gu), e_row))) and _close(y, want_y)
+
+
+def test_rows_are_independent_and_launch_is_deterministic(gpu):
+    H, I = 256, 128
+    ids, r, pairs = mc.routing(gpu)
+    T = ids.shape[0]
+    x, gu, dn = _random_case(H, I, 5)
+    h, y = _run(gpu, x, gu, dn, r)
+    h2, y2 = _run(gpu, x, gu, dn, r)
+    assert torch.equal(_bits(h), _bits(h2)) and torch.equal(_bits(y), _bits(y2))
+    perm = torch.randperm(T, generator=torch.Generator().manual_seed(9))
+    _, rp, pairs_p = mc.routing(gpu, ids[perm])
+    hp, yp = _run(gpu, x[perm], gu, dn, rp)
+    by_pair = lambda h_, p_: torch.empty_like(h_).index_copy_(0, p_, h_).view(T, K, -1)
+    assert torch.equal(_bits(by_pair(hp, pairs_p)), _bits(by_pair(h, pairs)[perm]))
+    assert torch.equal(_bits(yp.view(T, K, H)), _bits(y.view(T, K, H)[perm]))
 
 
 def _block(gpu):

@@ -1,4 +1,4 @@
-"""The CPU side of the block-scaled fp8 x fp8 MoE tile GEMM (moe_tile_f8.hip):
+"""The CPU side of the block-scaled fp8 x fp8 MoE tile GEMM (moe_tile_scaled.hip):
 ``moe_grouped_gemm(mx=True)`` on fp8 experts is the oracle of the GPU path, ``moe_uses_f8`` and the
 ``KernelPolicy.moe_tile_f8`` knob."""
 import pytest

@@ -1,5 +1,5 @@
 """The grouped block-scaled MFMA tile GEMM for fp8 experts on MX fp8 activations
-(csrc/kernels/moe_tile_f8.hip) on the GPU: both products bit for bit against fp64 and against the
+(csrc/kernels/moe_tile_scaled.hip) on the GPU: both products bit for bit against fp64 and against the
 widening fp8 tile kernel on exactly-summable operands with row counts on every edge of the 128-row
 tiling, random data against fp64 on the quantise-dequantised operands, row independence, the MoE
 block under ``KernelPolicy.moe_tile_f8`` (eager and in a captured graph) and the host checks."""
@@ -9,54 +9,17 @@ import pytest
 import torch
 
 import moe_tile_cases as mc
+from moe_tile_cases import (bits as _bits, close as _close, guarded as _guarded,
+                            products as _products, routing as _routing, swiglu64 as _swiglu64)
 from distributed_llm_inference import ops
 from distributed_llm_inference.config import ModelSpec
 from distributed_llm_inference.models.llama.modules import MoEMLP
 
 pytestmark = pytest.mark.gpu
 BF, FP8, U8 = torch.bfloat16, torch.float8_e4m3fn, torch.uint8
-SENT, G = -12345.0, 8
+SENT = mc.SENT
 E, K = mc.E, mc.K_TOP
 SHAPES = [(256, 128), (1152, 384)]
-ATOL, RTOL = 2e-2, 2e-2     # tests/test_moe_tile_q_gpu.py's oracle tolerance, elementwise
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
-
-
-def _close(got, want):
-    err = (got.double() - want.double()).abs()
-    print(f"max err {float(err.max()):.4g} of {float(want.abs().max()):.4g}")
-    return bool((err <= ATOL + RTOL * want.double().abs()).all())
-
-
-def _routing(gpu, ids=None):
-    ids = mc.explicit_ids() if ids is None else ids
-    r = ops.moe_group(ids.to(gpu), torch.ones(ids.shape, device=gpu), E)
-    return ids, r, r.sorted_pairs.cpu().long()
-
-
-def _guarded(fn, rows, width, gpu):
-    """fn(out) on a [rows + G, width] view between sentinel rows; the first ``rows`` rows."""
-    buf = torch.full((G + rows + G, width), SENT, dtype=BF, device=gpu)
-    fn(buf[G:])
-    torch.cuda.synchronize()
-    assert bool((buf[:G] == SENT).all()) and bool((buf[G + rows:] == SENT).all()), "guard rows"
-    return buf[G:G + rows].cpu()
-
-
-def _products(rows, wd, e_row):
-    """fp64 [P, N]: row j of ``rows [P, K]`` times expert ``e_row[j]`` of ``wd [E, N, K]``."""
-    out = torch.empty(rows.shape[0], wd.shape[1], dtype=torch.float64)
-    for e in range(E):
-        out[e_row == e] = rows[e_row == e] @ wd[e].t()
-    return out
-
-
-def _swiglu64(gu):
-    v = gu.reshape(gu.shape[0], -1, 2, 16)       # swiglu_interleave: 16 gate rows, 16 up rows
-    return (torch.nn.functional.silu(v[:, :, 0]) * v[:, :, 1]).reshape(gu.shape[0], -1)
 
 
 def _to(w, gpu):

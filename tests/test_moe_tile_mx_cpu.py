@@ -1,4 +1,4 @@
-"""The CPU side of the block-scaled MoE tile GEMM (moe_tile_mx.hip): ``moe_grouped_gemm(mx=True)``
+"""The CPU side of the block-scaled MoE tile GEMM (moe_tile_scaled.hip): ``moe_grouped_gemm(mx=True)``
 is the oracle of the GPU path, ``moe_uses_mx`` and the ``KernelPolicy.moe_tile_mx`` knob."""
 import pytest
 import torch
