@@ -277,7 +277,11 @@ __device__ __forceinline__ float block_reduce_max(float v, float* scratch) {
 }
 
 // ---- fp8 e4m3 (OCP "fn" encoding: gfx950's native fp8, identical to torch.float8_e4m3fn) ------
-// 4 floats -> 4 packed fp8 bytes (saturating conversion in hardware).
+// 4 floats -> 4 packed fp8 bytes, round to nearest even.  The bare conversion does NOT saturate:
+// on gfx950 every |x| >= 480 (464, the tie, still rounds to 448), +-inf included, comes out as
+// the NaN code 0x7F / 0xFF (tests/test_rope_oracle_gpu.py::test_fp8_overflow_bytes_observed
+// prints the bytes).  Callers that scale by the row's or block's amax first never exceed 448;
+// a caller with a fixed scale (the KV write) takes pack4_fp8_sat / f32_to_fp8_sat below.
 __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
   int r = 0;
   r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, r, false);
@@ -336,6 +340,17 @@ __device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(unsigned d, float s) {
 __device__ __forceinline__ uint8_t f32_to_fp8(float x) {
   return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(x, 0.f, 0, false) & 0xff);
 }
+
+// Saturating forms: finite values beyond +-448 and +-inf become +-448, NaN stays a NaN code (the
+// comparison is false for NaN); values within range are encoded exactly as by the bare forms.
+// Held to tests/rope_oracle.py's byte images by tests/test_rope_oracle_gpu.py.
+__device__ __forceinline__ float fp8_sat(float x) {
+  return fabsf(x) > 448.f ? copysignf(448.f, x) : x;
+}
+__device__ __forceinline__ unsigned pack4_fp8_sat(float a, float b, float c, float d) {
+  return pack4_fp8(fp8_sat(a), fp8_sat(b), fp8_sat(c), fp8_sat(d));
+}
+__device__ __forceinline__ uint8_t f32_to_fp8_sat(float x) { return f32_to_fp8(fp8_sat(x)); }
 
 __device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
 

@@ -71,8 +71,8 @@ __device__ __forceinline__ void gemv_store(const float (&v)[M][kRows], int wave,
           const size_t base = (((size_t)blk * rp.nkv + (h - rp.nh)) * rp.bs + off) * D;
           if (rp.kv_fp8) {
             uint8_t* kc = static_cast<uint8_t*>(rp.k_cache) + base;
-            gst<WT>(kc + d, (uint8_t)f32_to_fp8((float)o0 * rp.k_inv_scale));
-            gst<WT>(kc + d + half, (uint8_t)f32_to_fp8((float)o1 * rp.k_inv_scale));
+            gst<WT>(kc + d, (uint8_t)f32_to_fp8_sat((float)o0 * rp.k_inv_scale));
+            gst<WT>(kc + d + half, (uint8_t)f32_to_fp8_sat((float)o1 * rp.k_inv_scale));
           } else {
             bf16* kc = static_cast<bf16*>(rp.k_cache) + base;
             gst<WT>(kc + d, o0);
@@ -85,8 +85,8 @@ __device__ __forceinline__ void gemv_store(const float (&v)[M][kRows], int wave,
         const size_t i0 = (grp * D + dd) * 8 + (off & 7);
         if (rp.kv_fp8) {
           uint8_t* vc = static_cast<uint8_t*>(rp.v_cache);
-          gst<WT>(vc + i0, (uint8_t)f32_to_fp8((float)b0 * rp.v_inv_scale));
-          gst<WT>(vc + i0 + 8, (uint8_t)f32_to_fp8((float)b1 * rp.v_inv_scale));
+          gst<WT>(vc + i0, (uint8_t)f32_to_fp8_sat((float)b0 * rp.v_inv_scale));
+          gst<WT>(vc + i0 + 8, (uint8_t)f32_to_fp8_sat((float)b1 * rp.v_inv_scale));
         } else {
           bf16* vc = static_cast<bf16*>(rp.v_cache);
           gst<WT>(vc + i0, b0);

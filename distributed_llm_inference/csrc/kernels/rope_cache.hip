@@ -129,9 +129,9 @@ __global__ void __launch_bounds__(128) rope_cache_kernel(RopeCacheParams p) {
         uint8_t* dst = static_cast<uint8_t*>(p.k_cache) + base;
         const float s = p.k_inv_scale;
         *reinterpret_cast<unsigned*>(dst + i) =
-            pack4_fp8((float)oa[0] * s, (float)oa[1] * s, (float)oa[2] * s, (float)oa[3] * s);
+            pack4_fp8_sat((float)oa[0] * s, (float)oa[1] * s, (float)oa[2] * s, (float)oa[3] * s);
         *reinterpret_cast<unsigned*>(dst + half + i) =
-            pack4_fp8((float)ob[0] * s, (float)ob[1] * s, (float)ob[2] * s, (float)ob[3] * s);
+            pack4_fp8_sat((float)ob[0] * s, (float)ob[1] * s, (float)ob[2] * s, (float)ob[3] * s);
       } else {
         bf16* dst = static_cast<bf16*>(p.k_cache) + base;
         *reinterpret_cast<bf16x4*>(dst + i) = oa;
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(128) rope_cache_kernel(RopeCacheParams p) {
       const size_t e = ((grp + (size_t)kh * (p.bs >> 3)) * D + d) * 8 + (off & 7);
       const bf16 v = load_qkv1<NS>(p, row, t, vcol + it);
       if (FP8)
-        static_cast<uint8_t*>(p.v_cache)[e] = f32_to_fp8((float)v * p.v_inv_scale);
+        static_cast<uint8_t*>(p.v_cache)[e] = f32_to_fp8_sat((float)v * p.v_inv_scale);
       else
         static_cast<bf16*>(p.v_cache)[e] = v;
     }
@@ -282,10 +282,10 @@ __global__ void __launch_bounds__(ROPE_THREADS) rope_cache_kernel_v8(RopeCachePa
         uint8_t* dst = static_cast<uint8_t*>(p.k_cache) + base;
         const float s = p.k_inv_scale;
         uint2 va, vb;
-        va.x = pack4_fp8((float)oa[0] * s, (float)oa[1] * s, (float)oa[2] * s, (float)oa[3] * s);
-        va.y = pack4_fp8((float)oa[4] * s, (float)oa[5] * s, (float)oa[6] * s, (float)oa[7] * s);
-        vb.x = pack4_fp8((float)ob[0] * s, (float)ob[1] * s, (float)ob[2] * s, (float)ob[3] * s);
-        vb.y = pack4_fp8((float)ob[4] * s, (float)ob[5] * s, (float)ob[6] * s, (float)ob[7] * s);
+        va.x = pack4_fp8_sat((float)oa[0] * s, (float)oa[1] * s, (float)oa[2] * s, (float)oa[3] * s);
+        va.y = pack4_fp8_sat((float)oa[4] * s, (float)oa[5] * s, (float)oa[6] * s, (float)oa[7] * s);
+        vb.x = pack4_fp8_sat((float)ob[0] * s, (float)ob[1] * s, (float)ob[2] * s, (float)ob[3] * s);
+        vb.y = pack4_fp8_sat((float)ob[4] * s, (float)ob[5] * s, (float)ob[6] * s, (float)ob[7] * s);
         *reinterpret_cast<uint2*>(dst + i) = va;
         *reinterpret_cast<uint2*>(dst + half + i) = vb;
       } else {
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(ROPE_THREADS) rope_cache_kernel_v8(RopeCachePa
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (FP8)
-          static_cast<uint8_t*>(p.v_cache)[e0 + 8 * j] = f32_to_fp8((float)v[j] * p.v_inv_scale);
+          static_cast<uint8_t*>(p.v_cache)[e0 + 8 * j] = f32_to_fp8_sat((float)v[j] * p.v_inv_scale);
         else
           static_cast<bf16*>(p.v_cache)[e0 + 8 * j] = v[j];
       }

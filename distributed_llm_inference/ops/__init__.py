@@ -196,7 +196,8 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
                v_scale: float = 1.0, q_norm: Optional[torch.Tensor] = None,
                k_norm: Optional[torch.Tensor] = None, norm_eps: float = 1e-6):
     """Rotate q/k, write k/v to the paged cache; returns ``(q [T, nh, D], q_sink or None)``.
-    fp8 (e4m3fn) caches store ``k / k_scale`` and ``v / v_scale``.  ``qkv`` may be
+    fp8 (e4m3fn) caches store ``e4m3(x * fp32(1 / scale))``, finite values beyond +-448 and
+    +-inf saturated to +-448, NaN kept (``ref.fp8_kv_encode``).  ``qkv`` may be
     :class:`SplitKPartials` (summed while loaded, bit-identical to the reduce pass).
     ``q_norm`` / ``k_norm`` (Qwen3, both or neither): RMSNorm weights ``[head_dim]`` applied to
     every q / k head before the rotation, inside the same kernel (head_dim 32 / 64 / 128 / 256)."""

@@ -67,6 +67,15 @@ def _rotate(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
 
+def fp8_kv_encode(x: torch.Tensor, scale: float) -> torch.Tensor:
+    """What an fp8 KV cache stores for ``x``: e4m3 of ``x * fp32(1 / scale)`` -- a multiplication
+    by the fp32 reciprocal, as rope_cache.hip and the GEMV epilogue do, not a division -- with
+    finite values beyond +-448 and +-inf saturated to +-448; NaN stays NaN.  Returned as fp32
+    clamped to the e4m3 range (the caller's cast only rounds)."""
+    inv = torch.tensor(1.0 / scale, dtype=torch.float64).to(torch.float32)
+    return (x.float() * inv.to(x.device)).clamp(-448.0, 448.0)
+
+
 def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
                slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],
                nh: int, nkv: int, D: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
@@ -107,9 +116,9 @@ def rope_cache(qkv: torch.Tensor, positions: Optional[torch.Tensor],
             if k_cache.dtype == torch.bfloat16:
                 k_cache[blk, :, off, :] = kr[ok]
                 v_cache[blk, :, off // 8, :, off % 8] = v[ok]
-            else:  # fp8 cache: stored = x / scale (from the bf16-rounded value, as the kernel)
-                k_cache[blk, :, off, :] = (kr[ok].float() / k_scale).to(k_cache.dtype)
-                v_cache[blk, :, off // 8, :, off % 8] = (v[ok].float() / v_scale).to(v_cache.dtype)
+            else:  # fp8 cache, the kernels' rule (from the bf16-rounded value)
+                k_cache[blk, :, off, :] = fp8_kv_encode(kr[ok], k_scale).to(k_cache.dtype)
+                v_cache[blk, :, off // 8, :, off % 8] = fp8_kv_encode(v[ok], v_scale).to(v_cache.dtype)
     return qr.contiguous(), (q_sink.contiguous() if q_sink is not None else None)
 
 

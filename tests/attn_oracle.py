@@ -85,9 +85,13 @@ def slot_of(a, g: Geo):
 
 
 def _stored(x: torch.Tensor, scale: float, fp8: bool) -> torch.Tensor:
-    """What the cache holds for token values x: bf16, or e4m3 of x / scale."""
+    """What the cache holds for token values x: bf16, or e4m3 of x * fp32(1 / scale), saturated
+    at +-448 (the KV writers' rule, tests/rope_oracle.py)."""
     x = x.to(BF)
-    return (x.float() / scale).to(F8) if fp8 else x
+    if not fp8:
+        return x
+    inv = torch.tensor(1.0 / scale, dtype=torch.float64).float()
+    return (x.float() * inv).clamp(-448.0, 448.0).to(F8)
 
 
 def rounded(x: torch.Tensor, scale: float, fp8: bool) -> torch.Tensor:
