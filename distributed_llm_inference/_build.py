@@ -36,6 +36,7 @@ KERNEL_SOURCES = ["kernels/norm.hip", "kernels/activation.hip", "kernels/rope_ca
                   "kernels/moe.hip", "kernels/moe_tile.hip", "kernels/moe_tile_scaled.hip",
                   "kernels/moe_fp8_block.hip", "kernels/moe_tile_fp8_block.hip",
                   "kernels/gemm_fp8_block_small.hip", "kernels/gemm_fp8_block_tile.hip",
+                  "kernels/gemm_int4.hip",
                   "kernels/int8_outlier.hip", "kernels/digest.hip"]
 # sources compiled without packed fp32 instructions (v_pk_add/mul/fma_f32): scalar fp32 codegen
 NO_PACKED_FP32 = {"kernels/moe_tile_scaled.hip", "kernels/moe_fp8_block.hip",

@@ -45,6 +45,11 @@ def _common(ap: argparse.ArgumentParser) -> None:
                          "input features: 1 + 4/2048 byte per parameter) for every decoder-layer "
                          "linear and the routed experts; a 128x128 block-scaled FP8 checkpoint "
                          "runs on its stored bytes")
+    wq.add_argument("--int4", action="store_true",
+                    help="int4 group-quantised weights (uint4 + one fp16 scale and one 4-bit zero "
+                         "point per weight row and 128 input features: 1/2 + 3/128 byte per "
+                         "parameter) for every decoder-layer linear of a dense model; an AWQ / "
+                         "GPTQ checkpoint runs on its stored integers, no flag needed")
     wq.add_argument("--fp8-experts", action="store_true",
                     help="sparse-MoE models: fp8-e4m3 expert weights (one scale per weight row); "
                          "attention, norms, the router, dense layers and a shared expert stay bf16")
@@ -89,6 +94,7 @@ def engine_config(a):
     quantize = ("fp8" if a.fp8 else "int8" if a.int8
                 else "mxfp4" if getattr(a, "fp4", False)
                 else "fp8_block" if getattr(a, "fp8_block", False)
+                else "int4" if getattr(a, "int4", False)
                 else "fp8_experts" if getattr(a, "fp8_experts", False)
                 else "fp8_block_experts" if getattr(a, "fp8_block_experts", False)
                 else "mxfp4_experts" if getattr(a, "fp4_experts", False) else False)
@@ -127,7 +133,12 @@ def cmd_plan(a) -> int:
     # bytes per layer parameter: MXFP4 = a nibble + one scale byte per 32 (the norm weights, a
     # few thousand bf16 values per layer, are not told apart)
     # block-scaled fp8: a byte + one fp32 scale per 16 rows x 128 k
+    # int4: a nibble + an fp16 scale and a zero-point byte per 128 k of a row (also what an AWQ /
+    # GPTQ checkpoint holds with no flag given)
+    int4 = getattr(a, "int4", False) or (
+        str(spec.weight_quant).startswith("int4") and not (a.fp8 or a.int8 or a.fp4))
     per_param = (17 / 32 if a.fp4 else 1 + 4 / 2048 if getattr(a, "fp8_block", False)
+                 else 1 / 2 + 3 / 128 if int4
                  else (1 if (a.fp8 or a.int8) else 2))
     per_layer = int(spec.layer_param_count() * per_param)
     if getattr(a, "fp8_experts", False):

@@ -81,8 +81,21 @@ class ModelSpec:
     mlp_only_layers: Tuple[int, ...] = ()
     # how the checkpoint stores its linear weights: None (bf16 / fp16 / fp32 tensors) or
     # "fp8_block" (HF quantization_config quant_method "fp8": e4m3 bytes with an fp32
-    # weight_scale_inv per 128 x 128 block)
+    # weight_scale_inv per 128 x 128 block), "int4_awq" / "int4_gptq" (quant_method "awq" /
+    # "gptq": uint4 weights with an fp16 scale and a 4-bit zero point per 128 input features)
     weight_quant: Optional[str] = None
+    # "int4_gptq": the checkpoint_format "gptq_v2", whose qzeros hold the zero point itself
+    # (None / "gptq": zero point - 1)
+    weight_quant_format: Optional[str] = None
+
+    @property
+    def int4_checkpoint(self) -> Optional[str]:
+        """How an int4 checkpoint packs its integers -- "awq", "gptq" or "gptq_v2" -- else None."""
+        if self.weight_quant == "int4_awq":
+            return "awq"
+        if self.weight_quant == "int4_gptq":
+            return self.weight_quant_format or "gptq"
+        return None
 
     def __post_init__(self):
         if self.num_experts == 0:
@@ -316,6 +329,7 @@ class ModelSpec:
             eos = eos[0]
         return cls(
             weight_quant=_parse_quantization_config(cfg.get("quantization_config")),
+            weight_quant_format=_parse_quantization_format(cfg.get("quantization_config")),
             arch="llama",
             vocab_size=cfg["vocab_size"],
             hidden_size=h,
@@ -385,6 +399,13 @@ class ModelSpec:
             extra["quantization_config"] = dict(quant_method="fp8", fmt="e4m3",
                                                 activation_scheme="dynamic",
                                                 weight_block_size=[128, 128])
+        if self.weight_quant == "int4_awq":
+            extra["quantization_config"] = dict(quant_method="awq", bits=4, group_size=128,
+                                                zero_point=True, version="gemm")
+        if self.weight_quant == "int4_gptq":
+            extra["quantization_config"] = dict(
+                quant_method="gptq", bits=4, group_size=128, desc_act=False,
+                checkpoint_format=self.weight_quant_format or "gptq")
         if self.model_type in ("qwen2", "qwen3", "qwen3_moe", "qwen2_moe"):
             extra.update(use_sliding_window=self.sliding_window is not None,
                          sliding_window=self.sliding_window)
@@ -511,9 +532,12 @@ def _parse_quantization_config(q: Any) -> Optional[str]:
     with the offending field named."""
     if not q:
         return None
+    if q.get("quant_method") in ("awq", "gptq"):
+        return _parse_int4_config(q)
     if q.get("quant_method") != "fp8":
         raise ValueError(f"quantization_config.quant_method={q.get('quant_method')!r}: only "
-                         "\"fp8\" (128 x 128 block-scaled e4m3) checkpoints are supported")
+                         "\"fp8\" (128 x 128 block-scaled e4m3), \"awq\" and \"gptq\" (4-bit, "
+                         "group size 128) checkpoints are supported")
     if q.get("fmt", "e4m3") != "e4m3":
         raise ValueError(f"quantization_config.fmt={q.get('fmt')!r}: only \"e4m3\" is supported")
     wbs = q.get("weight_block_size")
@@ -521,6 +545,43 @@ def _parse_quantization_config(q: Any) -> Optional[str]:
         raise ValueError(f"quantization_config.weight_block_size={wbs!r}: only [128, 128] is "
                          "supported (per-tensor fp8 checkpoints are not)")
     return "fp8_block"
+
+
+def _parse_int4_config(q: dict) -> str:
+    """"int4_awq" / "int4_gptq" for exactly the 4-bit, group-size-128 AWQ ("gemm" version, with
+    zero points) and GPTQ (no act-order) checkpoints; anything else is refused with the offending
+    field named."""
+    method = q["quant_method"]
+    bits = q.get("bits", q.get("w_bit"))
+    if bits != 4:
+        raise ValueError(f"quantization_config.bits={bits!r}: only 4-bit {method} checkpoints "
+                         "are supported")
+    gs = q.get("group_size", q.get("q_group_size"))
+    if gs != 128:
+        raise ValueError(f"quantization_config.group_size={gs!r}: only group size 128 is "
+                         "supported")
+    if method == "awq":
+        if str(q.get("version", "gemm")).lower() != "gemm":
+            raise ValueError(f"quantization_config.version={q.get('version')!r}: only the "
+                             "\"gemm\" AWQ packing is supported")
+        if not q.get("zero_point", True):
+            raise ValueError("quantization_config.zero_point=False: only AWQ checkpoints with "
+                             "zero points are supported")
+        return "int4_awq"
+    if q.get("desc_act", False):
+        raise ValueError("quantization_config.desc_act=True: act-order GPTQ checkpoints are not "
+                         "supported")
+    if q.get("checkpoint_format", "gptq") not in ("gptq", "gptq_v2"):
+        raise ValueError(f"quantization_config.checkpoint_format={q.get('checkpoint_format')!r}: "
+                         "only \"gptq\" and \"gptq_v2\" are supported")
+    return "int4_gptq"
+
+
+def _parse_quantization_format(q: Any) -> Optional[str]:
+    """``ModelSpec.weight_quant_format``: "gptq_v2" for a GPTQ checkpoint of that format."""
+    if q and q.get("quant_method") == "gptq" and q.get("checkpoint_format") == "gptq_v2":
+        return "gptq_v2"
+    return None
 
 
 def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
@@ -536,6 +597,16 @@ def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
     if mode in ("fp8_experts", "mxfp4_experts", "fp8_block_experts") and not spec.num_experts:
         raise ValueError(f"{mode} needs a sparse MoE model; {spec.name} ({spec.model_type}) "
                          "has no experts")
+    if str(spec.weight_quant).startswith("int4"):
+        if spec.num_experts:
+            raise ValueError(f"{spec.name}: int4 (AWQ / GPTQ) checkpoints of sparse MoE models "
+                             "are not supported")
+        if mode not in (False, None, "none", "bf16", "int4"):
+            mode = "fp8" if mode is True else mode
+            raise ValueError(f"{mode}: {spec.name} is an int4 (AWQ / GPTQ) checkpoint, whose "
+                             "linears load as int4 (the default; \"bf16\" dequantises them); "
+                             "requantising them to another format is not supported")
+        return
     if spec.weight_quant and spec.num_experts and mode not in (False, None, "none", "bf16",
                                                                "fp8_block_experts", "fp8_block"):
         mode = "fp8" if mode is True else mode
@@ -550,7 +621,7 @@ def refuse_moe_quantization(spec: ModelSpec, mode: Any) -> None:
                          "expert weights, or fp8 expert weights as mode fp8_experts "
                          "(--fp8-experts), block-scaled fp8 expert weights as mode "
                          "fp8_block_experts (--fp8-block-experts), or MXFP4 expert weights as "
-                         "mode mxfp4_experts (--fp4-experts)")
+                         "mode mxfp4_experts (--fp4-experts); int4 covers dense models only")
 
 
 def resolve_model(model: Any) -> ModelSpec:

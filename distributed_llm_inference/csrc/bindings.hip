@@ -1126,6 +1126,57 @@ void linear_fp8_block(Tensor out, Tensor x, Tensor w, Tensor bscale, optional<Te
              "linear_fp8_block (tile)");
 }
 
+// int4 group-quantised weights (gemm_int4.hip): nibbles [N, K / 2] (uint8, ops.reference.pack_int4)
+// + fp16 scales [K / 128, N] + zero bytes [K / 128, N].  With x (1-32 bf16 rows): out [M, N] (or
+// [M, N / 2], swiglu) = x . dequant^T (+ bias) on the weight-streaming MFMA kernel.  Without x:
+// out [N, K] = the dequantised bf16 weight, for the products of more rows (ops.linear_int4)
+void linear_int4(Tensor out, optional<Tensor> x, Tensor w, Tensor scale, Tensor zero,
+                 optional<Tensor> bias, bool swiglu) {
+  CHECK_IN(out); CHECK_IN(w); CHECK_IN(scale); CHECK_IN(zero);
+  CHECK_BF16(out);
+  TORCH_CHECK(w.scalar_type() == at::kByte, "linear_int4: uint8 packed weights");
+  TORCH_CHECK(scale.scalar_type() == at::kHalf, "linear_int4: float16 scales");
+  TORCH_CHECK(zero.scalar_type() == at::kByte, "linear_int4: uint8 zero points");
+  TORCH_CHECK(out.dim() == 2 && w.dim() == 2 && scale.dim() == 2 && zero.dim() == 2,
+              "linear_int4: 2-D tensors");
+  const int64_t N = w.size(0), K = 2 * w.size(1);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24), "linear_int4: needs K % 128 == 0");
+  TORCH_CHECK(N >= 32 && N % 32 == 0 && N <= (1 << 24), "linear_int4: needs N % 32 == 0");
+  TORCH_CHECK(scale.size(0) == K / 128 && scale.size(1) == N && zero.size(0) == K / 128 &&
+                  zero.size(1) == N, "linear_int4: scales and zeros [K / 128, N]");
+  TORCH_CHECK(w.device() == out.device() && scale.device() == out.device() &&
+                  zero.device() == out.device(), "linear_int4: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(out.device());
+  const uint8_t* wp = w.data_ptr<uint8_t>();
+  const uint16_t* sp = static_cast<const uint16_t*>(scale.data_ptr());
+  const uint8_t* zp = zero.data_ptr<uint8_t>();
+  if (!x.has_value()) {
+    TORCH_CHECK(!bias.has_value() && !swiglu, "linear_int4: the dequantiser takes no epilogue");
+    TORCH_CHECK(out.size(0) == N && out.size(1) == K, "linear_int4: dequantised weight [N, K]");
+    check_rc(dli::launch_dequant_int4(bp(out), wp, sp, zp, (int)N, (int)K, cur_stream()),
+             "linear_int4 (dequantise)");
+    return;
+  }
+  CHECK_IN(*x); CHECK_BF16(*x);
+  TORCH_CHECK(x->dim() == 2 && x->size(1) == K && x->device() == out.device(),
+              "linear_int4: x [M, K] on the weight's device");
+  const int64_t M = x->size(0);
+  TORCH_CHECK(M >= 1 && M <= 32, "linear_int4: 1-32 rows (more run on the dequantised weight)");
+  TORCH_CHECK(!swiglu || !bias.has_value(), "linear_int4: swiglu takes no bias");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == (swiglu ? N / 2 : N),
+              "linear_int4: shape mismatch");
+  const dli::bf16* b = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N && bias->device() == out.device(),
+                "linear_int4: bias must have N entries");
+    b = bp(*bias);
+  }
+  check_rc(dli::launch_small_gemm_int4(bp(out), bp(*x), wp, sp, zp, b, (int)M, (int)N, (int)K,
+                                       swiglu, cur_stream()),
+           "linear_int4 (small)");
+}
+
 // ------------------------------------------------------------------------------ sparse MoE (moe.hip)
 // num_experts (with shared_w): logits [T, ld], ld > num_experts, column num_experts the shared
 // expert's gate logit; shared_w [T] gets its sigmoid
@@ -1689,6 +1740,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y = x . (W8 (.) block_scale)^T (+ bias), block-scaled fp8 weights (16 x 128 fp32 scales), "
         "bf16 rows: weight-streaming MFMA GEMM at 1-32 rows, LDS-staged MFMA tile GEMM beyond",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("block_scale"),
+        py::arg("bias") = py::none(), py::arg("swiglu") = false);
+  m.def("linear_int4", &linear_int4,
+        "int4 group-quantised weights (nibbles, fp16 scales and zero points per row and 128 k): "
+        "with x, y = x . dequant^T (+ bias) for 1-32 bf16 rows (weight-streaming MFMA GEMM); "
+        "without x, out = the dequantised bf16 weight",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("zero"),
         py::arg("bias") = py::none(), py::arg("swiglu") = false);
   m.def("moe_topk", &moe_topk, "router logits [T, E] -> top-k expert ids + bf16-rounded weights",
         py::arg("ids"), py::arg("w"), py::arg("logits"), py::arg("renorm"),

@@ -206,6 +206,17 @@ int launch_small_gemm_fp8_block(bf16* y, const bf16* x, const uint8_t* W, const 
 int launch_gemm_fp8_block_tile(bf16* y, const bf16* x, const uint8_t* W, const float* bscale,
                                const bf16* bias, int M, int N, int K, bool swiglu,
                                hipStream_t stream);
+// Int4 group-quantised weights (AWQ / GPTQ; gemm_int4.hip): W = unsigned nibbles [N, K / 2] in
+// ops.reference.pack_int4's order, scale = fp16 bits [K / 128, N], zero = bytes 0..15 [K / 128, N];
+// w[n, k] = (q[n, k] - zero[k / 128, n]) * scale[k / 128, n].  N % 32 == 0, K % 128 == 0.
+// 1 <= M <= 32 bf16 rows, weight-streaming on the bf16 MFMA: y[M, N] = x . w^T (+ bias).  swiglu:
+// the rows are swiglu_interleave'd gate|up (no bias), y is silu(gate) * up [M, N / 2]
+int launch_small_gemm_int4(bf16* y, const bf16* x, const uint8_t* W, const uint16_t* scale,
+                           const uint8_t* zero, const bf16* bias, int M, int N, int K, bool swiglu,
+                           hipStream_t stream);
+// out[N, K] (bf16) = bf16((q - zero) * scale), fp32 product, one rounding
+int launch_dequant_int4(bf16* out, const uint8_t* W, const uint16_t* scale, const uint8_t* zero,
+                        int N, int K, hipStream_t stream);
 // Sparse MoE MLP on bf16 expert weights (moe.hip).  P = T k (token, slot) pairs; E <= 256, k <= 8.
 // Every grid depends on (T, E, k, N) only and every count is read from device memory.
 // tile table capacity: min(E, P) + P / 32

@@ -91,6 +91,10 @@ class Linear(nn.Module):
         # block-scaled fp8: e4m3fn bytes [out, in] + fp32 scales [out / 16, in / 128]
         self.register_buffer("weight_fp8_block", None, persistent=False)
         self.register_buffer("weight_fp8_block_scale", None, persistent=False)
+        # int4 (AWQ / GPTQ): nibbles [out, in / 2] + fp16 scales and zero bytes [in / 128, out]
+        self.register_buffer("weight_int4", None, persistent=False)
+        self.register_buffer("weight_int4_scale", None, persistent=False)
+        self.register_buffer("weight_int4_zero", None, persistent=False)
         self.int8_threshold = 0.0
         # which projection of its layer this is ("qkv" / "o" / "gate_up" / "down", set by the
         # model): KernelPolicy.fp8_gemm4 routes fp8 products per role
@@ -152,6 +156,50 @@ class Linear(nn.Module):
         dev = self.weight.device
         self.weight_fp8_block = w8.to(dev).contiguous()
         self.weight_fp8_block_scale = scale.to(dev).contiguous()
+        if not keep_bf16:
+            self.weight = nn.Parameter(torch.empty(0, dtype=self.weight.dtype, device=dev),
+                                       requires_grad=False)
+
+    @property
+    def is_int4(self) -> bool:
+        """Int4 group-quantised weights (one fp16 scale and one 4-bit zero point per row and 128
+        input features; AWQ / GPTQ checkpoints or :meth:`quantize_int4`).  Every product is
+        :func:`ops.linear_int4` on bf16 rows."""
+        return self.weight_int4 is not None
+
+    def quantize_int4(self, keep_bf16: bool = False) -> bool:
+        """Quantise W with :func:`ops.quantize_int4` (round to nearest, asymmetric, per row and
+        128 input features).  Needs ``in_features % 128 == 0`` and ``out_features % 32 == 0``; a
+        Linear of any other shape is left as it is -- bf16 for good -- and False is returned.
+        Frees the bf16 copy unless asked not to.  Bias stays bf16."""
+        if not ops.int4_shape_ok(self.out_features, self.in_features):
+            return False
+        self.adopt_int4(*ops.quantize_int4(self.weight.data), keep_bf16=keep_bf16)
+        return True
+
+    def adopt_int4(self, wq: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor,
+                   keep_bf16: bool = False) -> None:
+        """Take packed nibbles ``[out, in / 2]`` (uint8, ops.reference.pack_int4), fp16 scales and
+        uint8 zero points ``[in / 128, out]`` as this Linear's weight.  No arithmetic touches
+        them.  Reserves the dequantise scratch of this device / stream for the products of more
+        than 32 rows (:class:`_Mxfp4Scratch`), so a forward never allocates it."""
+        N, K = self.out_features, self.in_features
+        if not ops.int4_shape_ok(N, K):
+            raise ValueError(f"int4 needs out % 32 == 0 and in % 128 == 0, got [{N}, {K}]")
+        if wq.dtype != torch.uint8 or tuple(wq.shape) != (N, K // 2):
+            raise ValueError(f"adopt_int4: uint8 nibbles [{N}, {K // 2}], got {wq.dtype} "
+                             f"{tuple(wq.shape)}")
+        if scale.dtype != torch.float16 or tuple(scale.shape) != (K // 128, N):
+            raise ValueError(f"adopt_int4: float16 scales [{K // 128}, {N}], got {scale.dtype} "
+                             f"{tuple(scale.shape)}")
+        if zero.dtype != torch.uint8 or tuple(zero.shape) != (K // 128, N):
+            raise ValueError(f"adopt_int4: uint8 zero points [{K // 128}, {N}], got {zero.dtype} "
+                             f"{tuple(zero.shape)}")
+        dev = self.weight.device
+        self.weight_int4 = wq.to(dev).contiguous()
+        self.weight_int4_scale = scale.to(dev).contiguous()
+        self.weight_int4_zero = zero.to(dev).contiguous()
+        MXFP4_SCRATCH.reserve(dev, N * K)
         if not keep_bf16:
             self.weight = nn.Parameter(torch.empty(0, dtype=self.weight.dtype, device=dev),
                                        requires_grad=False)
@@ -222,7 +270,8 @@ class Linear(nn.Module):
         """Split-K factor if ``gemm_tile`` takes this product on the GPU, else 0."""
         if (self.bias is not None or not x.is_cuda or x.dim() != 2 or x.dtype != torch.bfloat16
                 or not x.is_contiguous() or self.weight_fp8 is not None
-                or self.weight_int8 is not None or self.weight_fp8_block is not None):
+                or self.weight_int8 is not None or self.weight_fp8_block is not None
+                or self.weight_int4 is not None):
             return 0
         return ops.tile_gemm_splits(x.shape[0], self.out_features, self.in_features)
 
@@ -271,8 +320,9 @@ class Linear(nn.Module):
     def gemv_ok(self, rows: int, swiglu: bool = False, bf16_rows: bool = True) -> bool:
         """Whether :meth:`gemv` takes a product of ``rows`` GPU rows (bf16 rows, or with
         ``bf16_rows=False`` the fused quantiser's fp8 rows for fp8 weights)."""
-        if not 1 <= rows <= ops.SKINNY_DISPATCH_M or self.weight_fp8_block is not None:
-            return False   # block-scaled fp8: ops.linear_fp8_block takes 1-2 rows as well
+        if (not 1 <= rows <= ops.SKINNY_DISPATCH_M or self.weight_fp8_block is not None
+                or self.weight_int4 is not None):
+            return False   # block-scaled fp8 / int4: their own ops take 1-2 rows as well
         if swiglu and (self.bias is not None or self.out_features % 32):
             return False
         if self.weight_fp4 is not None:
@@ -358,6 +408,12 @@ class Linear(nn.Module):
             # beyond); a plain bf16 tensor, nothing deferred
             y = ops.linear_fp8_block(x.reshape(-1, self.in_features), self.weight_fp8_block,
                                      self.weight_fp8_block_scale, self.bias)
+            return y.reshape(*x.shape[:-1], self.out_features)
+        if self.weight_int4 is not None:
+            # int4 group-quantised weights on bf16 rows at any row count (csrc/kernels/
+            # gemm_int4.hip: weight-streaming at 1-32 rows, dequantise + the bf16 path beyond)
+            y = ops.linear_int4(x.reshape(-1, self.in_features), self.weight_int4,
+                                self.weight_int4_scale, self.weight_int4_zero, self.bias)
             return y.reshape(*x.shape[:-1], self.out_features)
         if self.weight_int8 is not None:
             if (x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= ops.SKINNY_DISPATCH_M
@@ -453,7 +509,8 @@ class Linear(nn.Module):
     def extra_repr(self) -> str:
         return (f"in={self.in_features}, out={self.out_features}, bias={self.bias is not None}, "
                 f"fp8={self.is_fp8}, int8={self.is_int8}, fp4={self.is_fp4}"
-                + (", fp8_block=True" if self.is_fp8_block else ""))
+                + (", fp8_block=True" if self.is_fp8_block else "")
+                + (", int4=True" if self.is_int4 else ""))
 
 
 @dataclass

@@ -130,6 +130,25 @@ class LlamaBlock(nn.Module):
                 layer.mlp.quantize_experts_fp8_block()
         return self
 
+    def quantize_int4(self) -> "LlamaBlock":
+        """Int4 group-quantised weights (uint4, one fp16 scale and one 4-bit zero point per row
+        and 128 input features; round to nearest, ops.quantize_int4) for every decoder-layer
+        linear of a dense model.  Linears that an AWQ / GPTQ checkpoint was loaded into hold
+        their stored integers already and are left as they are; a linear whose shape the kernels
+        do not take stays bf16 (Linear.quantize_int4).  Norms stay bf16."""
+        self._refuse_moe("int4")
+        for layer in self.layers:
+            mlp = layer.mlp
+            fused = mlp.fused_swiglu
+            if not mlp.gate_up_proj.is_int4:   # quantise the stored row order
+                mlp.set_fused_swiglu(False)
+            for lin in (layer.self_attn.qkv_proj, layer.self_attn.o_proj, mlp.gate_up_proj,
+                        mlp.down_proj):
+                if not lin.is_int4:
+                    lin.quantize_int4()
+            mlp.set_fused_swiglu(fused)
+        return self
+
     def quantize_experts_fp8(self) -> "LlamaBlock":
         """fp8 (e4m3, per-row scales) weights for the routed experts of every sparse-MoE layer;
         attention projections, norms, the router, dense layers and the shared expert stay bf16

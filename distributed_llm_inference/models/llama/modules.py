@@ -196,6 +196,12 @@ class LlamaMLP(nn.Module):
                     sc.copy_(sc[grp])
                 else:
                     sc[grp] = sc.clone()
+            elif w.is_int4:
+                # per-row groups along K: nibble rows, and the columns of the [K / 128, N] scale
+                # and zero-point tables, move together
+                w.weight_int4.copy_(perm(w.weight_int4))
+                for tab in (w.weight_int4_scale, w.weight_int4_zero):
+                    tab.copy_(perm(tab.t()).t())
             elif w.is_fp8:
                 # per-output-channel quantisation commutes with the row permutation
                 w.weight_fp8.copy_(perm(w.weight_fp8.view(torch.uint8)).view(w.weight_fp8.dtype))
@@ -218,6 +224,16 @@ class LlamaMLP(nn.Module):
             if self.fused_swiglu:
                 h = ops.linear_fp8_block(normed.reshape(-1, gp.in_features), gp.weight_fp8_block,
                                          gp.weight_fp8_block_scale, swiglu=True)
+                h = h.reshape(*normed.shape[:-1], self.intermediate_size)
+            else:
+                h = ops.silu_mul(gp(normed))
+            return self.down_proj(h, defer_reduce=defer_reduce)
+        if gp.is_int4:
+            # int4 gate|up on bf16 rows at any row count, SwiGLU in the kernel's epilogue (or after
+            # the dequantise path) once the rows are interleaved; down_proj dispatches itself
+            if self.fused_swiglu:
+                h = ops.linear_int4(normed.reshape(-1, gp.in_features), gp.weight_int4,
+                                    gp.weight_int4_scale, gp.weight_int4_zero, swiglu=True)
                 h = h.reshape(*normed.shape[:-1], self.intermediate_size)
             else:
                 h = ops.silu_mul(gp(normed))
@@ -607,6 +623,84 @@ def adopt_fp8_block_linear(lin: Linear, sd: dict, keys, interleave: bool = False
     return True
 
 
+_AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)   # nibble i of an AWQ word holds column 8 j + _AWQ_ORDER[i]
+
+
+def _nibbles(words: torch.Tensor, dim: int) -> torch.Tensor:
+    """The eight nibbles (bits 4 i .. 4 i + 3) of int32 ``words`` as a new axis of 8 at ``dim``."""
+    shape = [1] * (words.dim() + 1)
+    shape[dim] = 8
+    sh = (4 * torch.arange(8, device=words.device, dtype=torch.int32)).reshape(shape)
+    return ((words.unsqueeze(dim) >> sh) & 0xF).to(torch.uint8)
+
+
+def unpack_int4_checkpoint(sd: dict, key: str, fmt: str, K: int):
+    """The integers of one AWQ (``fmt`` "awq") or GPTQ ("gptq": qzeros store z - 1; "gptq_v2":
+    z) linear ``key`` (``key.qweight`` / ``.qzeros`` / ``.scales``, GPTQ: ``.g_idx``) as
+    ``(q [N, K] uint8, scale [K / 128, N] fp16, zero [K / 128, N] uint8)``, nothing rounded."""
+    qw, qz, sc = sd[key + ".qweight"], sd[key + ".qzeros"], sd[key + ".scales"]
+    if qw.dtype != torch.int32 or qz.dtype != torch.int32 or sc.dtype != torch.float16:
+        raise ValueError(f"{key}: int4 checkpoints hold int32 qweight / qzeros and float16 "
+                         f"scales, got {qw.dtype}, {qz.dtype}, {sc.dtype}")
+    G = K // 128
+    if K % 128 or sc.dim() != 2 or sc.shape[0] != G or sc.shape[1] % 8:
+        raise ValueError(f"{key}.scales: expected [{K} / 128, N] with N % 8 == 0, got "
+                         f"{tuple(sc.shape)}")
+    N = sc.shape[1]
+    if tuple(qz.shape) != (G, N // 8):
+        raise ValueError(f"{key}.qzeros: expected [{G}, {N // 8}], got {tuple(qz.shape)}")
+    if fmt == "awq":
+        if tuple(qw.shape) != (K, N // 8):
+            raise ValueError(f"{key}.qweight: expected [{K}, {N // 8}], got {tuple(qw.shape)}")
+        q = torch.empty(K, N // 8, 8, dtype=torch.uint8, device=qw.device)
+        z = torch.empty(G, N // 8, 8, dtype=torch.uint8, device=qw.device)
+        q[..., list(_AWQ_ORDER)] = _nibbles(qw, 2)
+        z[..., list(_AWQ_ORDER)] = _nibbles(qz, 2)
+        q, z = q.reshape(K, N), z.reshape(G, N)
+    else:
+        if tuple(qw.shape) != (K // 8, N):
+            raise ValueError(f"{key}.qweight: expected [{K // 8}, {N}], got {tuple(qw.shape)}")
+        g_idx = sd.get(key + ".g_idx")
+        if g_idx is not None and not torch.equal(
+                g_idx.long().reshape(-1), torch.arange(K, device=g_idx.device) // 128):
+            raise ValueError(f"{key}.g_idx is not k // 128: act-order (desc_act) GPTQ "
+                             "checkpoints are not supported")
+        q = _nibbles(qw, 1).reshape(K, N)
+        z = _nibbles(qz, 2).reshape(G, N)
+        if fmt != "gptq_v2":
+            z = (z + 1) & 15
+    return q.t().contiguous(), sc.contiguous(), z.contiguous()
+
+
+def load_int4_linear(lin: Linear, sd: dict, keys, fmt: str, interleave: bool = False,
+                     dequantize: bool = False) -> bool:
+    """Load one Linear from an AWQ / GPTQ checkpoint: the integers, scales and zero points of
+    ``keys`` (q|k|v, gate|up, or a single ``*.weight`` name), concatenated along the output
+    features, are repacked (ops.reference.pack_int4) and adopted as they are -- never
+    requantised.  ``interleave``: rows to ops.swiglu_interleave order, q, scale and zero point
+    together.  ``dequantize`` (the "bf16" mode), or a shape the int4 kernels do not take: the
+    weight becomes ``bf16((q - z) * s)`` instead.  Returns False, touching nothing, when the
+    checkpoint holds these linears unquantised."""
+    stems = [k[:-len(".weight")] for k in keys]
+    if not all(s + ".qweight" in sd for s in stems):
+        return False
+    parts = [unpack_int4_checkpoint(sd, s, fmt, lin.in_features) for s in stems]
+    q = torch.cat([p[0] for p in parts], 0)
+    scale, zero = (torch.cat([p[i] for p in parts], 1) for i in (1, 2))
+    if q.shape[0] != lin.out_features:
+        raise ValueError(f"{stems[0]}: {q.shape[0]} output features in the checkpoint, "
+                         f"{lin.out_features} in the model")
+    if interleave:
+        src = ops._swiglu_src(lin.out_features, q.device)
+        q, scale, zero = q[src], scale[:, src], zero[:, src]
+    wq = ops.reference.pack_int4(q)
+    if dequantize or not ops.int4_shape_ok(lin.out_features, lin.in_features):
+        lin.weight.copy_(ops.reference.dequant_int4(wq, scale, zero, lin.weight.dtype))
+    else:
+        lin.adopt_int4(wq, scale.contiguous(), zero.contiguous())
+    return True
+
+
 class LlamaDecoderLayer(nn.Module):
     """One decoder layer; ``layer_idx`` is the GLOBAL layer index (as in the reference)."""
 
@@ -706,11 +800,14 @@ class LlamaDecoderLayer(nn.Module):
         return self.mlp(None, x_q=xq, defer_reduce=defer_out), res_out
 
     # ------------------------------------------------------------------ weights
-    def load_hf_state_dict(self, sd: dict, keep_fp8_block: bool = False) -> None:
+    def load_hf_state_dict(self, sd: dict, keep_fp8_block: bool = False,
+                           int4: Optional[str] = None, int4_dequantize: bool = False) -> None:
         """Load a HF ``LlamaDecoderLayer`` state dict (keys relative to ``model.layers.{i}.``),
         fusing q|k|v and gate|up into the single GEMM weights.  ``keep_fp8_block`` (the
         "fp8_block" mode): the linears of a 128 x 128 block-scaled FP8 checkpoint keep their
-        stored bytes (:func:`adopt_fp8_block_linear`) instead of becoming bf16."""
+        stored bytes (:func:`adopt_fp8_block_linear`) instead of becoming bf16.  ``int4``: the
+        state dict is an AWQ ("awq") or GPTQ ("gptq" / "gptq_v2") checkpoint's, whose linears are
+        adopted as stored (:func:`load_int4_linear`), or with ``int4_dequantize`` become bf16."""
         def g(k):
             if k not in sd:
                 raise KeyError(f"parameter {k} not found in state dict for layer {self.layer_idx}")
@@ -720,6 +817,10 @@ class LlamaDecoderLayer(nn.Module):
         dt = self.input_layernorm.weight.dtype
         with torch.no_grad():
             def adopt(lin, *keys, interleave=False):
+                if int4:
+                    if self.is_moe:
+                        raise ValueError("int4 checkpoints of sparse MoE models are not supported")
+                    return load_int4_linear(lin, sd, keys, int4, interleave, int4_dequantize)
                 return keep_fp8_block and adopt_fp8_block_linear(lin, sd, keys, interleave)
             if not adopt(self.self_attn.qkv_proj, "self_attn.q_proj.weight",
                          "self_attn.k_proj.weight", "self_attn.v_proj.weight"):

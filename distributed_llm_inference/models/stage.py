@@ -31,7 +31,9 @@ def apply_quantization(block, mode, threshold: float = 6.0):
     mode changes nothing; on bf16 experts it quantises them), or "fp8_block" (that format for
     every decoder-layer linear -- qkv, o, gate|up, down, a shared expert -- and the routed experts;
     what a 128 x 128 FP8 checkpoint loaded under this mode holds already is left as it is;
-    embedding, LM head, router and norms stay bf16).  "bf16" also dequantises experts
+    embedding, LM head, router and norms stay bf16), or "int4" (dense Llama-family models: uint4
+    weights with one fp16 scale and one zero point per row and 128 input features for every
+    decoder-layer linear; what an AWQ / GPTQ checkpoint loaded is left as it is).  "bf16" also dequantises experts
     that were loaded from such a checkpoint; False / None / "none" leave them as loaded."""
     if mode == "bf16" and hasattr(block, "dequantize_experts"):
         return block.dequantize_experts()
@@ -51,6 +53,11 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise NotImplementedError(f"block-scaled fp8 weights are not implemented for "
                                       f"{type(block).__name__} (Llama-family blocks only)")
         return block.quantize_fp8_block()
+    if mode == "int4":
+        if not hasattr(block, "quantize_int4"):
+            raise NotImplementedError(f"int4 weights are not implemented for "
+                                      f"{type(block).__name__} (Llama-family blocks only)")
+        return block.quantize_int4()
     if mode == "fp8_experts":
         if not hasattr(block, "quantize_experts_fp8"):
             raise ValueError(f"fp8_experts needs a sparse MoE model; {type(block).__name__} has "
@@ -66,7 +73,7 @@ def apply_quantization(block, mode, threshold: float = 6.0):
             raise ValueError(f"fp8_block_experts needs a sparse MoE model; "
                              f"{type(block).__name__} has no experts")
         return block.quantize_experts_fp8_block()
-    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / fp8_block / "
+    raise ValueError(f"unknown quantisation mode {mode!r} (expected fp8 / int8 / mxfp4 / fp8_block / int4 / "
                      "fp8_experts / fp8_block_experts / mxfp4_experts)")
 
 

@@ -1475,6 +1475,114 @@ def linear_fp8_block(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
     return out
 
 
+INT4_SMALL_MAX_M = 32   # rows of gemm_int4.hip's weight-streaming kernel; more dequantise
+
+
+def int4_shape_ok(N: int, K: int) -> bool:
+    """The shapes the int4 kernels take: whole 128-k scale groups, whole 32-row workgroups."""
+    return N > 0 and K > 0 and N % 32 == 0 and K % ref.INT4_GROUP == 0
+
+
+def quantize_int4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Round-to-nearest asymmetric 4-bit quantisation of a [N, K] weight per (row, 128-k group),
+    on ``w``'s device: ``s = fp16((max - min) / 15)`` (1 where the group is constant; at least
+    fp16's smallest normal), ``z = clamp(round(-min / s), 0, 15)``, ``q = clamp(round(w / s) + z,
+    0, 15)``.  Returns ``(wq uint8 [N, K / 2]`` in :func:`reference.pack_int4`'s order, ``scale``
+    fp16 [K / 128, N], ``zero`` uint8 [K / 128, N]) -- the layout of AWQ / GPTQ checkpoints'
+    tables.  This code is also the CPU oracle of the quantiser."""
+    if w.dim() != 2 or not int4_shape_ok(*w.shape):
+        raise ValueError(f"quantize_int4: [N, K] with N % 32 == 0 and K % {ref.INT4_GROUP} == 0, "
+                         f"got {tuple(w.shape)}")
+    N, K = w.shape
+    G = K // ref.INT4_GROUP
+    wq = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(G, N, dtype=torch.float16, device=w.device)
+    zero = torch.empty(G, N, dtype=torch.uint8, device=w.device)
+    step = max(1, (1 << 24) // K)   # rows per chunk: bounded fp32 temporaries
+    for i in range(0, N, step):
+        g = w[i:i + step].float().reshape(-1, G, ref.INT4_GROUP)
+        if not bool(torch.isfinite(g).all()):
+            raise ValueError("quantize_int4: NaN or Inf in the weight")
+        lo, hi = g.amin(-1, keepdim=True), g.amax(-1, keepdim=True)
+        s = ((hi - lo) / 15).clamp_(min=2.0 ** -14, max=65504.0).to(torch.float16)
+        s = torch.where(hi > lo, s, torch.ones_like(s)).float()
+        z = torch.round(-lo / s).clamp_(0, 15)
+        q = (torch.round(g / s) + z).clamp_(0, 15)
+        wq[i:i + step] = ref.pack_int4(q.reshape(-1, K))
+        scale[:, i:i + step] = s[..., 0].t().to(torch.float16)
+        zero[:, i:i + step] = z[..., 0].t().to(torch.uint8)
+    return wq, scale, zero
+
+
+def linear_int4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, swiglu: bool = False) -> torch.Tensor:
+    """``y = x . w^T (+ bias)`` for bf16 rows ``x [M, K]`` and an int4 group-quantised weight (AWQ /
+    GPTQ checkpoints, :func:`quantize_int4`): ``wq`` uint8 [N, K / 2] (:func:`reference.pack_int4`),
+    ``scale`` fp16 [K / 128, N], ``zero`` uint8 [K / 128, N] with values 0..15,
+    ``w[n, k] = (q[n, k] - zero[k / 128, n]) * scale[k / 128, n]``.  N % 32 == 0, K % 128 == 0.
+    1-32 rows: the weight-streaming MFMA kernel of gemm_int4.hip -- the nibbles widened in
+    registers, zero point and scale applied to each group's fp32 sum, one bf16 rounding.  More
+    rows: its dequantiser writes ``bf16((q - zero) * scale)`` into the per-device scratch
+    (models/common.py; reserved by ``Linear.adopt_int4``, a temporary when none is) and the bf16
+    GEMM path runs on it.  ``swiglu``: the rows are a swiglu_interleave'd gate|up weight (no
+    bias), returns silu(gate) * up ``[M, N / 2]``.  CPU: the torch oracle (fp32 ``x @
+    dequant.T``, one rounding)."""
+    name = "linear_int4"
+    if x.dim() != 2 or wq.dim() != 2 or scale.dim() != 2 or zero.dim() != 2:
+        raise ValueError(f"{name}: x [M, K], wq [N, K / 2], scale and zero [K / 128, N] are 2-D, "
+                         f"got x {tuple(x.shape)}, wq {tuple(wq.shape)}, scale "
+                         f"{tuple(scale.shape)}, zero {tuple(zero.shape)}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: x must be bfloat16, got {x.dtype}")
+    if wq.dtype != torch.uint8:
+        raise ValueError(f"{name}: wq must be uint8 (packed nibbles), got {wq.dtype}")
+    if scale.dtype != torch.float16:
+        raise ValueError(f"{name}: scale must be float16, got {scale.dtype}")
+    if zero.dtype != torch.uint8:
+        raise ValueError(f"{name}: zero must be uint8, got {zero.dtype}")
+    M, K = x.shape
+    N = wq.shape[0]
+    if M < 1:
+        raise ValueError(f"{name}: x needs at least one row")
+    if K == 0 or K % ref.INT4_GROUP or wq.shape[1] * 2 != K:
+        raise ValueError(f"{name}: K % 128 == 0 and wq [N, K / 2] must match x [M, K], got "
+                         f"x {tuple(x.shape)}, wq {tuple(wq.shape)}")
+    if N == 0 or N % 32:
+        raise ValueError(f"{name}: N % 32 == 0, got wq {tuple(wq.shape)}")
+    G = K // ref.INT4_GROUP
+    if tuple(scale.shape) != (G, N):
+        raise ValueError(f"{name}: scale must be [K / 128, N] = [{G}, {N}], got "
+                         f"{tuple(scale.shape)}")
+    if tuple(zero.shape) != (G, N):
+        raise ValueError(f"{name}: zero must be [K / 128, N] = [{G}, {N}], got "
+                         f"{tuple(zero.shape)}")
+    if bias is not None and (swiglu or bias.dtype != torch.bfloat16 or bias.numel() != N):
+        raise ValueError(f"{name}: bias must be {N} bfloat16 values and is not taken with swiglu")
+    if not (wq.is_contiguous() and scale.is_contiguous() and zero.is_contiguous()):
+        raise ValueError(f"{name}: wq, scale and zero must be contiguous")
+    if not _gpu(x):
+        y = x.float() @ ref.dequant_int4(wq, scale, zero, torch.float32).t()
+        if bias is not None:
+            y = y + bias.float()
+        return _swiglu_ref(y) if swiglu else y.to(torch.bfloat16)
+    x = x.contiguous()
+    if M <= INT4_SMALL_MAX_M:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=x.device)
+        native().linear_int4(out, x, wq, scale, zero, bias, swiglu)
+        return out
+    # more rows: dequantise, then the bf16 path a bf16 Linear of this shape takes
+    from ..models.common import MXFP4_SCRATCH
+    try:
+        buf = MXFP4_SCRATCH.get(x.device, N * K)
+    except RuntimeError:   # no Linear reserved one (a bare call): a temporary
+        buf = torch.empty(N * K, dtype=torch.bfloat16, device=x.device)
+    w = buf.view(-1)[:N * K].view(N, K)
+    native().linear_int4(w, None, wq, scale, zero)
+    sp = tile_gemm_splits(M, N, K) if bias is None else 0
+    y = gemm_tile(x, w, splits=sp) if sp else torch.nn.functional.linear(x, w, bias)
+    return swiglu_interleaved(y) if swiglu else y
+
+
 def skinny_gemm_qkv_rope(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor],
                          bias: Optional[torch.Tensor], positions: Optional[torch.Tensor],
                          slot_mapping: Optional[torch.Tensor], cos_sin: Optional[torch.Tensor],

@@ -445,8 +445,47 @@ def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor
     return out
 
 
+# ----------------------------------------------------------------------------- int4 (AWQ / GPTQ)
+INT4_GROUP = 128   # input features per (scale, zero point) of a weight row
+# nibble p (bits 4 p .. 4 p + 3) of a packed 32-bit word holds element INT4_ORDER[p] of its eight
+# consecutive k: elements 2 m and 2 m + 1 sit 16 bits apart, a bf16 pair after one shift and one
+# and-or (csrc/kernels/gemm_int4.hip).  This pair of functions is the only place the order lives
+INT4_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def pack_int4(q: torch.Tensor) -> torch.Tensor:
+    """Unsigned 4-bit values ``q [N, K]`` (any integer dtype, 0..15, K % 8 == 0) as the bytes the
+    int4 kernels read: uint8 ``[N, K / 2]``, little-endian 32-bit words of eight nibbles in
+    :data:`INT4_ORDER`."""
+    N, K = q.shape
+    if K % 8:
+        raise ValueError(f"pack_int4: K % 8 == 0, got {tuple(q.shape)}")
+    n = q.to(torch.uint8).reshape(N, K // 8, 8)[..., list(INT4_ORDER)]   # nibble p of each word
+    return (n[..., 0::2] | (n[..., 1::2] << 4)).reshape(N, K // 2).contiguous()
+
+
+def unpack_int4(packed: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`pack_int4`: uint8 ``[N, K]`` values 0..15."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    n = torch.stack([packed & 0xF, packed >> 4], dim=-1).reshape(N, K // 8, 8)
+    q = torch.empty_like(n)
+    q[..., list(INT4_ORDER)] = n
+    return q.reshape(N, K)
+
+
+def dequant_int4(packed: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor,
+                 dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """``w[n, k] = (q[n, k] - zero[k / 128, n]) * scale[k / 128, n]`` of an int4 group-quantised
+    weight (``packed`` uint8 [N, K / 2], ``scale`` fp16 [K / 128, N], ``zero`` uint8 [K / 128,
+    N]): the product in fp32 (exact), then one rounding to ``dtype`` (torch.float32: none)."""
+    q = unpack_int4(packed).float()
+    s = scale.float().t().repeat_interleave(INT4_GROUP, 1)
+    z = zero.float().t().repeat_interleave(INT4_GROUP, 1)
+    return ((q - z) * s).to(dtype)
+
+
 # ----------------------------------------------------------------------------- sparse MoE
-MOE_MAX_EXPERTS = 256   # csrc/kernels/moe.hip limits
+MOE_MAX_EXPERTS = 256  # csrc/kernels/moe.hip limits
 MOE_MAX_TOPK = 8
 MOE_TILE_ROWS = 32
 

@@ -154,7 +154,10 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
     mode given and everything else as bf16; "bf16" dequantises the experts too, and the other
     quantising modes are refused -- but "fp8_block", under which every decoder-layer linear of
     such a checkpoint keeps its stored bytes as well (on a bf16 checkpoint or random init the mode
-    quantises them)."""
+    quantises them).  "int4": uint4 weights with an fp16 scale and a zero point per row and 128
+    input features (dense Llama-family models); an AWQ / GPTQ 4-bit group-128 checkpoint loads its
+    linears in that format as stored with no mode given, "bf16" dequantises them, and the other
+    quantising modes are refused."""
     spec = _load_config(model_name, cache_dir, token)
     refuse_moe_quantization(spec, use_quantized)
     log.info("building %s block for layers %s", spec.name, list(layer_ids))
@@ -168,6 +171,9 @@ def load_block(model_name: str, layer_ids: Sequence[int], use_quantized: bool = 
             sd = get_block_state_dict(model_name, layer.layer_idx, cache_dir, token, prefix_fmt)
             if use_quantized == "fp8_block" and spec.arch == "llama":
                 layer.load_hf_state_dict(sd, keep_fp8_block=True)   # the stored bytes stay
+            elif spec.int4_checkpoint:   # AWQ / GPTQ: the stored integers stay ("bf16": not)
+                layer.load_hf_state_dict(sd, int4=spec.int4_checkpoint,
+                                         int4_dequantize=use_quantized == "bf16")
             else:
                 layer.load_hf_state_dict(sd)
     apply_quantization(block, use_quantized)
@@ -204,10 +210,12 @@ def convert_to_optimized_block(block, quantize=False, threshold: float = 5.0, de
 
 # --------------------------------------------------------------------------- whole stages
 def load_stage_weights(stage: CausalLMStage, model_name: str, cache_dir=None, token=False,
-                       keep_fp8_block: bool = False) -> None:
+                       keep_fp8_block: bool = False, int4_dequantize: bool = False) -> None:
     """Load layers + (embedding / final norm / LM head, if owned) of a stage from a checkpoint.
     ``keep_fp8_block`` (the "fp8_block" mode): the decoder-layer linears of a 128 x 128
-    block-scaled FP8 checkpoint keep their stored bytes."""
+    block-scaled FP8 checkpoint keep their stored bytes.  An AWQ / GPTQ checkpoint
+    (``spec.int4_checkpoint``) loads its linears as int4, as stored; ``int4_dequantize`` (the
+    "bf16" mode) makes them bf16."""
     spec = stage.spec
     files = _weight_files(model_name, cache_dir, token)
     needed_prefixes = []
@@ -223,6 +231,9 @@ def load_stage_weights(stage: CausalLMStage, model_name: str, cache_dir=None, to
         sd = get_block_state_dict(model_name, layer.layer_idx, cache_dir, token, lp)
         if keep_fp8_block and spec.arch == "llama":
             layer.load_hf_state_dict(sd, keep_fp8_block=True)
+        elif spec.int4_checkpoint:
+            layer.load_hf_state_dict(sd, int4=spec.int4_checkpoint,
+                                     int4_dequantize=int4_dequantize)
         else:
             layer.load_hf_state_dict(sd)
     want = []
@@ -315,7 +326,8 @@ def build_stage(model: str, start: int, end: int, device=None, dtype=torch.bfloa
     if random_init and checkpoint is None:
         stage.init_random(seed)
     else:
-        load_stage_weights(stage, checkpoint or model, keep_fp8_block=quantize == "fp8_block")
+        load_stage_weights(stage, checkpoint or model, keep_fp8_block=quantize == "fp8_block",
+                           int4_dequantize=quantize == "bf16")
     stage.quantize(quantize, int8_threshold)
     return stage
 
